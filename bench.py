@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: batched LFT backward sweeps/s (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
                     [--workload lft|config3|config5|select_gains|bruteforce]
     torchrun --nproc-per-node N bench.py --gpus N ...      (driver form, N > 1)
 
@@ -9,6 +9,15 @@ A "step" is one pass of the hot path over one batch: the fused LFT sweep
 (stage + prefix compose + all-horizon query) of every problem plus the fused
 horizon argmin, with the (T*, J*) all-gather over RCCL when N > 1.  Inputs are
 synthetic blocks resident in HBM before timing.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`,
+`ms_per_step` and the roofline fields derived from the timed steps.  --full adds
+every figure that takes a run of its own (the CPU baseline, the PCIe-inclusive
+rate, the config-4 anchors, the selects from the raw linearisation, the fp64 s = 5
+augmented blocks, the other block layout); without it those fields are null or
+absent.  --dump-outputs DIR writes what the last timed step returned (J, status,
+T*, J*, ...) as DIR/<name>.npy: the inputs are seeded, so two builds of the library
+can be compared output for output.
 
 Workloads (BASELINE.json configs):
   lft (default)  N=1: config 2 -- Quadrotor shape s=13, m=4, N=100, 4096 problems, fp64.
@@ -285,7 +294,7 @@ def _lft_workload(args, world, lo, hi, dev):
 
         host, alt = (At.data, Bt.data, Qt.data, Ri, z0, QTt.data), launch_bm
 
-    side = _traj64_side(hi - lo, s, m, N, t_min, dtype, dev) if tiled else None
+    side = _traj64_side(hi - lo, s, m, N, t_min, dtype, dev) if tiled and not args.no_alt else None
     if (s, m, args.dtype) == (13, 4, "f64") and not tiled and world == 1 and not args.no_alt:
         side = _quad_side(hi - lo, N, t_min, dev)
     kname, bound = kernel_path(s, m, args.dtype, hi - lo)
@@ -651,6 +660,45 @@ def _dry_workload(args, world, lo, hi, dev):
     return mod.workload(args, world, lo, hi, dev)
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(dirpath, result, gathered=None):
+    """--dump-outputs: every tensor of the last timed step's result (J, status, t_star,
+    j_star, ...) as <dirpath>/<name>.npy, floating tensors in their own precision
+    (float32 / float64), integer ones as float64 (exact).  With N > 1 rank 0 writes its
+    own shard and the gathered (T*, J*).  Above DUMP_BUDGET_BYTES in all, the per-problem
+    tensors (leading dimension = the result's batch) keep one fixed, seeded sample of
+    problems, the same rows in every tensor, listed in sample_index.npy."""
+    import numpy as np
+    import torch
+    named = {k: v for k, v in vars(result).items() if isinstance(v, torch.Tensor)}
+    if gathered is not None:
+        named["gathered_t_star"], named["gathered_j_star"] = gathered
+
+    def width(t):
+        return 4 if t.dtype == torch.float32 else 8
+
+    Bn = int(result.status.shape[0])
+    per_problem = {k for k, v in named.items() if v.dim() >= 1 and v.shape[0] == Bn}
+    total = sum(v.numel() * width(v) for v in named.values())
+    idx = None
+    if total > DUMP_BUDGET_BYTES and per_problem:
+        fixed = sum(named[k].numel() * width(named[k]) for k in named if k not in per_problem)
+        row = sum(named[k].numel() // Bn * width(named[k]) for k in per_problem) + 8
+        keep = max(1, min(Bn, (DUMP_BUDGET_BYTES - fixed) // row))
+        idx = np.sort(np.random.default_rng(0).choice(Bn, size=keep, replace=False))
+    os.makedirs(dirpath, exist_ok=True)
+    for name, t in named.items():
+        if idx is not None and name in per_problem:
+            t = t.index_select(0, torch.as_tensor(idx, device=t.device))
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(dirpath, name + ".npy"),
+                a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+    if idx is not None:
+        np.save(os.path.join(dirpath, "sample_index.npy"), idx.astype(np.float64))
+
+
 def args_with_batch(args, batch):
     import copy
     a = copy.copy(args)
@@ -711,9 +759,21 @@ def main(argv=None):
     ap.add_argument("--global-batch", type=int, default=None,
                     help="--scaling strong: problems over all GPUs (default: 8 x the "
                          "workload's per-GPU size; lft: config 4's 262,144)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline, the "
+                         "PCIe-inclusive rate, the config-4 anchors, the selects from the raw "
+                         "linearisation, the fp64 s = 5 augmented blocks and the other block "
+                         "layout (each can still be left out with its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes the tensors the last timed step "
+                         "returned to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if not args.full:  # a plain run: the timed steps and nothing beside them
+        args.no_cpu_baseline = args.no_h2d = args.no_alt = args.no_anchor = True
 
     from time_opt_ilqr_amd import distributed as hd
     launched = "WORLD_SIZE" in os.environ
@@ -867,6 +927,8 @@ def main(argv=None):
         ok = torch.tensor([0 if status_ok else 1], dtype=torch.int32, device=dev)
         hd.all_reduce_max(ok)
         status_ok = int(ok.item()) == 0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, r, gathered if world > 1 else None)
     if dry:
         if rank == 0 and args.dry_out:
             import numpy as np
@@ -1067,6 +1129,7 @@ def main(argv=None):
             "prewarm_launches": prewarm,
             "ms_per_step": elapsed / K * 1e3,
             "higher_is_better": True,
+            "full": args.full,
             "scaling": args.scaling,
             "vs_baseline": None,
             "dtype": args.dtype,

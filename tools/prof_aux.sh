@@ -7,7 +7,7 @@ OUT=gpurun_out/$1
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/cfg3 -o run --output-format csv -- \
-  python3 bench.py --s 5 --m 1 --N 200 --batch 65536 --dtype f32 --t-min 20 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/cfg3.log 2>&1 && \
+  python3 bench.py --full --s 5 --m 1 --N 200 --batch 65536 --dtype f32 --t-min 20 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/cfg3.log 2>&1 && \
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/traj -o run --output-format csv -- \
   python3 tools/bench_traj.py --rounds 3 > $OUT/traj.log 2>&1 && \
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/traj3 -o run --output-format csv -- \
