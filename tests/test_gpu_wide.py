@@ -1,0 +1,441 @@
+"""The wide fp64 path (17 <= s <= 32, include/hop_wide.h) against the NumPy oracle and
+against the narrow kernels on the shapes both can run."""
+import os
+
+import numpy as np
+import pytest
+
+from oracle import hop_oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+
+def _t(x, dev, dtype=None):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype or torch.float64, device=dev)
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+def _rel(got, ref):
+    got = np.asarray(got, dtype=np.float64)
+    ref = np.asarray(ref, dtype=np.float64)
+    return float(np.max(np.abs(got - ref)) / max(np.max(np.abs(ref)), 1e-300))
+
+
+def _elem_rel(got, ref):
+    got = np.asarray(got, dtype=np.float64)
+    ref = np.asarray(ref, dtype=np.float64)
+    return float(np.max(np.abs(got - ref) / np.abs(ref)))
+
+
+def _wide_sweep(dev, A, Bm, Q, Ri, z0, QT, t_min=0, t_max=0):
+    """hop_lft_sweep_wide_f64 called directly (the engine routes s <= 16 to the narrow
+    kernels); Ri is [m, m] or [B, m, m], z0 [s]."""
+    import torch
+    from time_opt_ilqr_amd import _lib
+    lib = _lib.load()
+    Bn, N, s, _ = A.shape
+    m = Bm.shape[-1]
+    tA, tB, tQ, tR, tz, tQT = (_t(x, dev) for x in (A, Bm, Q, Ri, z0, QT))
+    J = torch.empty((Bn, N), dtype=torch.float64, device=dev)
+    st = torch.empty((Bn,), dtype=torch.int32, device=dev)
+    ts = torch.empty((Bn,), dtype=torch.int32, device=dev)
+    js = torch.empty((Bn,), dtype=torch.float64, device=dev)
+    r_bs = 0 if np.ndim(Ri) == 2 else m * m
+    _lib.check(lib.hop_lft_sweep_wide_f64(
+        _lib.ptr(tA), _lib.ptr(tB), _lib.ptr(tQ), _lib.ptr(tR), r_bs, 0, 1, _lib.ptr(tQT),
+        _lib.ptr(tz), 0, Bn, N, N, s, m, 8, t_min, t_max, _lib.ptr(J), _lib.ptr(st),
+        _lib.ptr(ts), _lib.ptr(js), None, None, _lib.stream_handle(dev)))
+    torch.cuda.synchronize()
+    return _np(J), _np(st), _np(ts), _np(js)
+
+
+# 1 -------------------------------------------------------------------------
+@pytest.mark.parametrize("s,m,N,Bn", [(17, 4, 12, 5), (24, 6, 12, 5), (31, 3, 12, 5),
+                                      (32, 8, 12, 5), (32, 16, 6, 3), (20, 1, 40, 3),
+                                      (32, 8, 1, 2)])
+def test_wide_block_form_vs_oracle(dev, s, m, N, Bn):
+    from time_opt_ilqr_amd import engine
+    A, Bm, Q, R, Ri, z0, QT = orc.synth_lft_batch(7000 + s, Bn, s, m, N)
+    t_min = min(2, N)  # the N = 1 case has the one horizon only
+    res = engine.propagate(_t(A, dev), _t(Bm, dev), _t(Q, dev), _t(Ri, dev), _t(z0[0], dev),
+                           _t(QT, dev), t_min=t_min, t_max=N, return_efg=True,
+                           return_prefix=True)
+    Jo, sto = orc.lft_sweep_batch(A, Bm, Q, Ri, z0[0], QT)
+    assert sto.tolist() == [0] * Bn
+    assert _np(res.status).tolist() == [0] * Bn
+    J = _np(res.J)
+    print("J elementwise relative error", _elem_rel(J, Jo))
+    assert _elem_rel(J, Jo) <= 1e-9
+    To, _ = orc.select_horizon(Jo, t_min, N)
+    assert _np(res.t_star).tolist() == To.tolist()
+    efg, pre = _np(res.efg), _np(res.prefix)
+    for b in range(Bn):
+        o = orc.lft_sweep(A[b], Bm[b], Q[b], Ri[b], z0[b], QT[b], want_efg=True,
+                          want_prefix=True)
+        for i, key in enumerate(("E", "F", "G")):
+            assert _rel(efg[b, :, i], o[key]) <= 1e-9, (b, key)
+        for i, key in enumerate(("Ebar", "Fbar", "Gbar")):
+            assert _rel(pre[b, :, i], o[key]) <= 1e-9, (b, key)
+
+
+# 2 -------------------------------------------------------------------------
+@pytest.mark.parametrize("s,m", [(13, 4), (16, 6)])
+def test_wide_kernel_on_narrow_shapes(dev, s, m):
+    from time_opt_ilqr_amd import _lib, engine
+    Bn, N = 6, 20
+    A, Bm, Q, R, Ri, z0, QT = orc.synth_lft_batch(7100 + s, Bn, s, m, N)
+    J, st, _, _ = _wide_sweep(dev, A, Bm, Q, Ri, z0[0], QT)
+    with _lib.options(force_generic=True):
+        ref = engine.propagate(_t(A, dev), _t(Bm, dev), _t(Q, dev), _t(Ri, dev), _t(z0[0], dev),
+                               _t(QT, dev))
+    print("wide vs generic", _elem_rel(J, _np(ref.J)))
+    assert _elem_rel(J, _np(ref.J)) <= 1e-10
+    assert st.tolist() == _np(ref.status).tolist()
+
+
+# 3 -------------------------------------------------------------------------
+def test_wide_padding_invariance(dev):
+    """an s = 13 problem embedded block-decoupled into s = 24 gives the narrow J"""
+    from time_opt_ilqr_amd import engine
+    A, Bm, Q, R, Ri, z0, QT = orc.synth_lft_problem(7200, 13, 4, 20)
+    Ap, Bp, Qp, Rp, zp, QTp = orc.embed_block_decoupled(A, Bm, Q, Ri, z0, QT, 24, 6)
+    r1 = engine.propagate(_t(A[None], dev), _t(Bm[None], dev), _t(Q[None], dev), _t(Ri, dev),
+                          _t(z0, dev), _t(QT[None], dev))
+    r2 = engine.propagate(_t(Ap[None], dev), _t(Bp[None], dev), _t(Qp[None], dev), _t(Rp, dev),
+                          _t(zp, dev), _t(QTp[None], dev))
+    assert _np(r2.status).tolist() == [0]
+    print("embedded vs narrow", _elem_rel(_np(r2.J), _np(r1.J)))
+    assert _elem_rel(_np(r2.J), _np(r1.J)) <= 1e-10
+
+
+# 4 -------------------------------------------------------------------------
+def test_wide_batch_tail_permutation_and_prefix(dev):
+    import torch
+    from time_opt_ilqr_amd import engine
+    Bn, s, m, N = 37, 20, 3, 10
+    A, Bm, Q, R, Ri, z0, QT = orc.synth_lft_batch(7300, Bn, s, m, N)
+    A[36], Bm[36], Q[36], Ri[36], QT[36] = A[5], Bm[5], Q[5], Ri[5], QT[5]
+    args = [_t(x, dev) for x in (A, Bm, Q, Ri, z0[0], QT)]
+    r1 = engine.propagate(*args)
+    assert _np(r1.status).tolist() == [0] * Bn
+    perm = np.random.default_rng(0).permutation(Bn)
+    args_p = [_t(x[perm], dev) for x in (A, Bm, Q, Ri)] + [_t(z0[0], dev), _t(QT[perm], dev)]
+    r2 = engine.propagate(*args_p)
+    assert torch.equal(r2.J, r1.J[torch.as_tensor(perm, device=dev)])
+    r3 = engine.propagate(*args, n_use=4)
+    assert torch.equal(r3.J, r1.J[:, :4])
+    assert torch.equal(r1.J[36], r1.J[5])
+    Jo, _ = orc.lft_sweep_batch(A[[0, 17, 36]], Bm[[0, 17, 36]], Q[[0, 17, 36]], Ri[[0, 17, 36]],
+                                z0[0], QT[[0, 17, 36]])
+    assert _elem_rel(_np(r1.J)[[0, 17, 36]], Jo) <= 1e-9
+
+
+# 5 -------------------------------------------------------------------------
+@pytest.mark.parametrize("s", [20, 32])
+def test_wide_status_bits_and_nonfinite(dev, s):
+    """the recipe of test_lft_status_bits_and_nonfinite: jitter without LU, the LU slot,
+    NaN only at the poisoned horizon"""
+    from time_opt_ilqr_amd import engine
+    A, Bm, Q, R, Ri, z0, QT = orc.synth_lft_batch(900, 3, s, 1, 6)
+    Q = Q.copy()
+    Q[0, 2] = Q[0, 2] - np.eye(s) * (np.linalg.eigvalsh(Q[0, 2]).min() + 5e-8)  # needs jitter
+    Q[1, 3] = -np.eye(s)                                                     # LU fallback
+    QT = QT.copy()
+    QT[2, 4, 0, 0] = np.nan
+    res = engine.propagate(_t(A, dev), _t(Bm, dev), _t(Q, dev), _t(Ri, dev), _t(z0[0], dev),
+                           _t(QT, dev))
+    st = _np(res.status)
+    J = _np(res.J)
+    o0 = orc.lft_sweep(A[0], Bm[0], Q[0], Ri[0], z0[0], QT[0])
+    o1 = orc.lft_sweep(A[1], Bm[1], Q[1], Ri[1], z0[1], QT[1])
+    print("status", st.tolist(), "oracle", o0["status"], o1["status"])
+    assert st[0] & orc.ST_JITTER and not st[0] & orc.ST_LU
+    assert o0["status"] & orc.ST_JITTER
+    assert st[1] & orc.ST_LU and o1["status"] & orc.ST_LU
+    print("J errors", _elem_rel(J[0, :2], o0["J"][:2]), _elem_rel(J[0], o0["J"]),
+          _elem_rel(J[1], o1["J"]))
+    assert _elem_rel(J[0, :2], o0["J"][:2]) <= 1e-6
+    assert _elem_rel(J[0], o0["J"]) <= 1e-1
+    assert np.isfinite(J[1]).all() and _elem_rel(J[1], o1["J"]) <= 1e-6
+    assert st[2] & orc.ST_NONFINITE
+    assert np.isnan(J[2, 4]) and np.isfinite(np.delete(J[2], 4)).all()
+
+
+# 6 -------------------------------------------------------------------------
+def test_wide_window_argmin(dev):
+    from time_opt_ilqr_amd import engine
+    s, m, N, Bn = 24, 4, 12, 4
+    A, Bm, Q, R, Ri, z0, QT = orc.synth_lft_batch(7400, Bn, s, m, N)
+    QT = QT.copy()
+    QT[1, 6, 0, 0] = np.nan   # horizon 7, inside the window: NaN wins
+    QT[2, 1, 0, 0] = np.nan   # horizon 2, outside
+    res = engine.propagate(_t(A, dev), _t(Bm, dev), _t(Q, dev), _t(Ri, dev), _t(z0[0], dev),
+                           _t(QT, dev), t_min=5, t_max=9)
+    Jo, _ = orc.lft_sweep_batch(A, Bm, Q, Ri, z0[0], QT)
+    To, Jso = orc.select_horizon(Jo, 5, 9)
+    assert _np(res.t_star).tolist() == To.tolist()
+    assert int(_np(res.t_star)[1]) == 7
+    got = _np(res.j_star)
+    assert np.array_equal(np.isnan(got), np.isnan(Jso))
+    assert _elem_rel(got[~np.isnan(got)], Jso[~np.isnan(Jso)]) <= 1e-9
+    # the fused argmin is the separate argmin kernel on the same curve, bitwise
+    ts2, js2 = engine.select_horizon(res.J, 5, 9)
+    assert _np(ts2).tolist() == _np(res.t_star).tolist()
+
+
+# 7 -------------------------------------------------------------------------
+def _traj_batch(seeds, n, m, N):
+    ps = [orc.synth_traj_problem(int(s), n, m, N) for s in seeds]
+    st = {k: np.stack([p[k] for p in ps]) for k in ("A", "B", "a_res", "X", "U", "xg", "u_ref",
+                                                     "Q", "R", "alpha", "w")}
+    st["P"] = np.stack([orc.terminal_weight(p["alpha"], n) for p in ps])
+    st["R_inv"] = np.stack([orc.spd_inverse(orc.sym(p["R"]))[0] for p in ps])
+    st["wrap_idx"] = ps[0]["wrap_idx"]
+    return ps, st
+
+
+def _traj_blocks(p, rho, extra=None):
+    Aa, Ba, Qa, _, z0, Ri = orc.augment_stage(list(p["A"]), list(p["B"]), p["a_res"], p["X"],
+                                              p["U"], p["xg"], p["u_ref"], p["Q"], p["R"],
+                                              p["w"], wrap_idx=p["wrap_idx"], rho_reg=rho,
+                                              extra=extra)
+    QT = orc.augment_terminal(p["X"], p["xg"], p["alpha"], wrap_idx=p["wrap_idx"], rho_reg=rho)
+    return Aa, Ba, Qa, Ri, z0, QT
+
+
+def _traj_dev_args(st, dev):
+    return [_t(st[k], dev) for k in ("A", "B", "a_res", "X", "U", "xg", "u_ref", "Q")]
+
+
+@pytest.mark.parametrize("n,m,N,extra", [(16, 4, 10, False), (24, 6, 10, True),
+                                         (31, 8, 10, False)])
+def test_wide_augment_matches_oracle_builders(dev, n, m, N, extra):
+    from time_opt_ilqr_amd import engine
+    ps, st = _traj_batch(range(900, 907), n, m, N)
+    Bn = len(ps)
+    kw = {}
+    if extra:  # PSD cxx, cx and c per (problem, step)
+        rng = np.random.default_rng(5)
+        M = rng.standard_normal((Bn, N, n, n))
+        cxx = M @ M.transpose(0, 1, 3, 2) / n
+        cx = 0.3 * rng.standard_normal((Bn, N, n))
+        c0 = rng.uniform(0.0, 1.0, (Bn, N))
+        kw = dict(qxx_extra=_t(cxx, dev), qx_extra=_t(cx, dev), c_extra=_t(c0, dev))
+    out = engine.augment(*_traj_dev_args(st, dev), _t(st["P"], dev), _t(st["w"], dev),
+                         wrap_idx=st["wrap_idx"], **kw)
+    for b, p in enumerate(ps):
+        ex = None
+        if extra:
+            def ex(x, u, b=b, p=p):
+                k = int(np.argmin(np.abs(p["X"][:N] - x).sum(axis=1)))
+                return c0[b, k], cx[b, k], cxx[b, k]
+        Aa, Ba, Qa, Ri, z0, QT = _traj_blocks(p, 1e-12, ex)
+        for name, got, ref in (("A", out.A, Aa), ("B", out.B, Ba), ("Q", out.Q, Qa),
+                               ("QT", out.QT, QT)):
+            print(n, b, name, _rel(_np(got[b]), ref))
+            assert _rel(_np(got[b]), ref) <= 1e-14, (b, name)
+        bottom = np.zeros((N, n + 1))
+        bottom[:, n] = 1.0
+        assert np.array_equal(_np(out.A[b, :, n, :]), bottom)
+        assert np.array_equal(_np(out.B[b, :, n, :]), np.zeros((N, m)))
+        assert np.array_equal(_np(out.A[b, :, :n, :n]), st["A"][b])
+    assert _np(out.z0).tolist() == [0.0] * n + [1.0]
+
+
+# 8 -------------------------------------------------------------------------
+@pytest.mark.parametrize("n,m", [(16, 4), (24, 6), (31, 8)])
+def test_wide_trajectory_form(dev, n, m):
+    """the bars of test_traj_sweep_vs_reference_goldens on the wide builder + sweep"""
+    from time_opt_ilqr_amd import engine
+    N = 24
+    n_use = N - 3
+    ps, st = _traj_batch(range(900, 906), n, m, N)
+    for rho in (1.0, 1e-12):
+        res = engine.propagate_traj(*_traj_dev_args(st, dev), _t(st["R_inv"], dev),
+                                    _t(st["P"], dev), _t(st["w"], dev), wrap_idx=st["wrap_idx"],
+                                    rho_reg=rho, n_use=n_use, t_min=5, t_max=n_use)
+        J = _np(res.J)
+        Jref = np.stack([orc.lft_sweep(*_traj_blocks(p, rho), n_use)["J"] for p in ps])
+        print(n, rho, "J max-norm relative", _rel(J, Jref))
+        if rho == 1.0:
+            assert _rel(J, Jref) <= 1e-9
+            assert (_np(res.status) == 0).all()
+            Tref, _ = orc.select_horizon(Jref, 5, n_use)
+            assert _np(res.t_star).tolist() == Tref.tolist()
+        else:
+            assert np.isfinite(J).all()
+            assert _rel(J, Jref) <= 5e-2
+
+
+# 9 -------------------------------------------------------------------------
+@pytest.mark.parametrize("n,m,N,extra", [(17, 4, 12, False), (24, 16, 8, True),
+                                         (31, 8, 12, False)])
+def test_wide_riccati_vs_oracle(dev, n, m, N, extra):
+    from gain_check import assert_per_step
+    from time_opt_ilqr_amd import engine
+    probs = [orc.synth_riccati_problem(7600 + i, n, m, N) for i in range(6)]
+    cnt = len(probs)
+    kw, ex = {}, [None] * cnt
+    if extra:  # the extra stage cost: PSD cxx, cx and c per (problem, step)
+        rng = np.random.default_rng(6)
+        M = rng.standard_normal((cnt, N, n, n))
+        cxx = 0.05 * M @ M.transpose(0, 1, 3, 2) / n
+        cx = 0.1 * rng.standard_normal((cnt, N, n))
+        c0 = rng.uniform(0.0, 0.5, (cnt, N))
+        kw = dict(qxx_extra=_t(cxx, dev), qx_extra=_t(cx, dev), c_extra=_t(c0, dev))
+
+        def make(b):
+            Xb = probs[b][2]
+            return lambda x, u: (lambda k: (c0[b, k], cx[b, k], cxx[b, k]))(
+                int(np.argmin(np.abs(Xb[:N] - x).sum(axis=1))))
+        ex = [make(b) for b in range(cnt)]
+    stk = lambda j: np.stack([p[j] for p in probs])  # noqa: E731
+    A, B, X, U, xg, ur, Q, R = (stk(j) for j in range(8))
+    R = R.copy()
+    R[5] = -np.eye(m) * 50.0  # negative definite: Quu_reg fails the Cholesky gate
+    Qf = np.stack([orc.terminal_weight(p[8], n) for p in probs])
+    T = np.array([1, 2, N // 2, N - 1, N, N], dtype=np.int32)
+    wrap = [1]
+    lm = 1e-3
+    args = [_t(x, dev) for x in (A, B, X, U, xg, ur, Q, R, Qf)]
+    r0 = engine.riccati(*args, T, lm, mode=0, wrap_idx=wrap, want_v=True, **kw)
+    r1 = engine.riccati(*[a[:5] for a in args], T[:5], lm, mode=1, w_stage=0.3, wrap_idx=wrap,
+                        **{k: v[:5] for k, v in kw.items()})
+    st0 = _np(r0.status)
+    assert st0[:5].tolist() == [0] * 5
+    assert _np(r1.status).tolist() == [0] * 5
+    for i in range(5):
+        Ti = int(T[i])
+        p = probs[i]
+        ks, Ks, ok, Vxxs, Vxs = orc.riccati_truncated(
+            list(A[i]), list(B[i]), X[i], U[i], xg[i], ur[i], Q[i], R[i], p[8], Ti,
+            lm_lambda=lm, wrap_idx=wrap, want_v=True, extra=ex[i])
+        assert ok
+        assert_per_step(_np(r0.k[i, :Ti]), np.array(ks), 1e-6, f"{i} k")
+        assert_per_step(_np(r0.K[i, :Ti]), np.array(Ks), 1e-6, f"{i} K")
+        assert_per_step(_np(r0.Vxx[i, :Ti + 1]), np.array(Vxxs), 1e-6, f"{i} Vxx0")
+        assert_per_step(_np(r0.Vx[i, :Ti + 1]), np.array(Vxs), 1e-6, f"{i} Vx0")
+        Vxx, Vx, V0, K, k = orc.riccati_expand(
+            list(A[i]), list(B[i]), X[i], U[i], xg[i], ur[i], Q[i], R[i], p[8], Ti, 0,
+            lm_lambda=lm, w_stage=0.3, wrap_idx=wrap, extra=ex[i])
+        assert_per_step(_np(r1.K[i, :Ti]), np.array(K), 1e-6, f"{i} K1")
+        assert_per_step(_np(r1.k[i, :Ti]), np.array(k), 1e-6, f"{i} k1")
+        assert_per_step(_np(r1.Vxx[i, :Ti + 1]), np.array(Vxx), 1e-6, f"{i} Vxx")
+        assert_per_step(_np(r1.Vx[i, :Ti + 1]), np.array(Vx), 1e-6, f"{i} Vx")
+        assert_per_step(_np(r1.V0[i, :Ti + 1]), np.array(V0), 1e-6, f"{i} V0")
+    # the negative-definite R: the oracle reports failure, the kernel ST_FAIL
+    _, _, ok = orc.riccati_truncated(list(A[5]), list(B[5]), X[5], U[5], xg[5], ur[5], Q[5],
+                                     R[5], probs[5][8], int(T[5]), lm_lambda=lm, wrap_idx=wrap,
+                                     extra=ex[5])
+    assert ok is False
+    assert st0[5] & orc.ST_FAIL
+
+
+# 10 ------------------------------------------------------------------------
+def _chain_dynamics(n, m, dt):
+    """the mass-spring chain of tests/golden/make_golden_wide.py (same expressions)"""
+    p = n // 2
+    act = [j * p // m for j in range(m)]
+    k, ks, c = 2.0, 0.5, 0.3
+
+    def F(x, u):
+        x = np.asarray(x, dtype=float).reshape(-1)
+        u = np.asarray(u, dtype=float).reshape(-1)
+        q, v = x[:p], x[p:]
+        ext = np.concatenate(([0.0], q, [0.0]))
+        d = np.diff(ext)
+        f = k * d + ks * np.sin(d)
+        acc = f[1:] - f[:-1] - c * v
+        for j, i in enumerate(act):
+            acc[i] += u[j]
+        return np.concatenate((q + dt * v, v + dt * acc))
+
+    return F
+
+
+@pytest.mark.parametrize("n", [16, 24, 30])
+def test_wide_solver_vs_reference(dev, golden_dir, n):
+    """solver.ilqr_timeopt(F=callable) against the reference's own solves
+    (wide_solve_*.npz; every select of every stored trial has an argmin gap >= 1e-3)"""
+    from time_opt_ilqr_amd import solver
+    for trial in range(3):
+        d = np.load(os.path.join(golden_dir, f"wide_solve_n{n}_{trial}.npz"))
+        assert float(d["gaps"].min()) >= 1e-3
+        m = int(d["m"])
+        F = _chain_dynamics(n, m, float(d["dt"]))
+        sol = solver.ilqr_timeopt(F, d["x0"], d["xg"], d["u_ref"], d["Q"], d["R"],
+                                  float(d["alpha"]), float(d["w"]), int(d["N"]), int(d["T_min"]),
+                                  int(d["T_max"]), method="propagator",
+                                  max_iter=int(d["max_iter"]))
+        assert list(sol["T_hist"]) == d["T_hist"].tolist(), (trial, sol["T_hist"])
+        err = _elem_rel(np.asarray(sol["J_hist"]), d["J_hist"])
+        print(n, trial, "J_hist relative error", err)
+        assert err <= 1e-6
+
+
+def test_wide_dropins_and_rejections(dev):
+    """the reference-named drop-ins at n = 20 (a raw R_list is inverted on the host),
+    and what the wide shapes refuse"""
+    import torch
+    from time_opt_ilqr_amd import engine, horizon_selection as hs
+    s, m, N = 21, 3, 8
+    A, Bm, Q, R, Ri, z0, QT = orc.synth_lft_problem(7700, s, m, N)
+    Jo = orc.lft_sweep(A, Bm, Q, Ri, z0, QT)["J"]
+    J1 = hs.propagator_all_Jt_aug(list(A), list(Bm), list(Q), [R] * N, z0, list(QT))
+    J2 = hs.propagator_all_Jt_aug(list(A), list(Bm), list(Q), [R] * N, z0, list(QT),
+                                  R_inv_cached=Ri)
+    assert _elem_rel(J1, Jo) <= 1e-9 and _elem_rel(J2, Jo) <= 1e-9
+    n = s - 1
+    Ar, Br, X, U, xg, ur, Qc, Rc, alpha = orc.synth_riccati_problem(7701, n, m, N)
+    k, K, ok = hs.backward_pass_truncated(list(Ar), list(Br), X, U, xg, ur, Qc, Rc, alpha, N)
+    ks, Ks, oko = orc.riccati_truncated(list(Ar), list(Br), X, U, xg, ur, Qc, Rc, alpha, N)
+    assert ok and oko
+    assert _rel(np.array(K), np.array(Ks)) <= 1e-6 and _rel(np.array(k), np.array(ks)) <= 1e-6
+    args = [_t(x[None], dev) for x in (A, Bm, Q)] + [_t(Ri, dev), _t(z0, dev), _t(QT[None], dev)]
+    with pytest.raises(ValueError, match="utils.chol_inv"):
+        engine.propagate(*args, r_is_inverse=False)
+    with pytest.raises(ValueError, match="utils.chol_inv"):  # per-step raw R
+        engine.propagate(args[0], args[1], args[2], _t(np.stack([R] * N)[None], dev), args[4],
+                         args[5], r_is_inverse=False)
+    with pytest.raises(ValueError, match="utils.chol_inv"):
+        engine.propagate(*[a.to(torch.float32) for a in args])
+    t64 = lambda x, r, c: engine.Tile64(torch.zeros((1, N, r * c, 64), device=dev), 1, r, c)  # noqa: E731
+    with pytest.raises(ValueError, match="utils.chol_inv"):
+        engine.propagate(t64(A, s, s), t64(Bm, s, m), t64(Q, s, s), args[3], args[4],
+                         t64(QT, s, s))
+    with pytest.raises(_lib_error()):  # the brute-force curve stays narrow
+        engine.bruteforce_jcurve(_t(Ar[None], dev), _t(Br[None], dev), _t(X[None], dev),
+                                 _t(U[None], dev), _t(xg, dev), _t(ur, dev), _t(Qc, dev),
+                                 _t(Rc, dev), _t(orc.terminal_weight(alpha, n), dev), N)
+
+
+def _lib_error():
+    from time_opt_ilqr_amd import _lib
+    return _lib.HopError
+
+
+# 11 ------------------------------------------------------------------------
+def test_integration_md_wide_ctypes_stub_runs(dev):
+    """INTEGRATION.md's wide ctypes stub runs as written at s = 17 and agrees with engine"""
+    import re
+    from time_opt_ilqr_amd import _lib, engine
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(repo, "INTEGRATION.md")).read()
+    blocks = [b for b in re.findall(r"```python\n(.*?)```", text, re.S)
+              if "hop_lft_sweep_wide_f64" in b]
+    assert len(blocks) == 1
+    ns = {}
+    code = blocks[0].replace("/path/to/time_opt_ilqr_amd/libhop_amd.so", _lib.LIB_PATH)
+    exec(compile(code, "INTEGRATION.md", "exec"), ns)
+    A, Bm, Q, R, Ri, z0, QT = orc.synth_lft_batch(7500, 2, 17, 2, 8)
+    J, st, ts = ns["propagator_all_Jt_aug_wide_batched"](A, Bm, Q, Ri[0], z0[0], QT, 8, 3, 8)
+    r = engine.propagate(_t(A, dev), _t(Bm, dev), _t(Q, dev), _t(Ri[0], dev), _t(z0[0], dev),
+                         _t(QT, dev), t_min=3, t_max=8)
+    assert np.array_equal(J, _np(r.J)) and np.array_equal(ts, _np(r.t_star))
+    assert (st == 0).all()
+    Jo, _ = orc.lft_sweep_batch(A, Bm, Q, Ri[0], z0[0], QT)
+    assert _elem_rel(J, Jo) <= 1e-9

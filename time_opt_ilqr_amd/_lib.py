@@ -20,6 +20,7 @@ ST_LU = 2
 ST_NONFINITE = 4
 ST_FAIL = 8
 MAX_DIM = 16
+WIDE_MAX_DIM = 32  # include/hop_wide.h: s = n + 1 <= 32 on the wide (fp64) entries
 
 _P = C.c_void_p
 _I32 = C.c_int32
@@ -113,6 +114,13 @@ SIGNATURES = {
     "hop_ilqr_select_mask": (C.c_int, [_I64, _P, _P, _P, _P, _P, _P]),
 }
 
+# include/hop_wide.h (the fp64 entries for 17 <= s <= 32); bound beside SIGNATURES
+WIDE_SIGNATURES = {
+    "hop_lft_sweep_wide_f64": (C.c_int, _LFT),
+    "hop_augment_wide_f64": (C.c_int, _TRJ64 + _AUG_TAIL),
+    "hop_riccati_wide_f64": (C.c_int, _RIC64),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -137,9 +145,10 @@ def load(path: str | None = None):
         # the library's launches then see no device (measured: HIP error 100)
         import torch  # noqa: F401
         lib = C.CDLL(p)
-        for name, (res, args) in SIGNATURES.items():
-            if path is not None and not hasattr(lib, name):
-                continue  # an older build loaded for an A/B (tools/ab_libs.py)
+        other = path is not None or "HOP_LIB" in os.environ
+        for name, (res, args) in list(SIGNATURES.items()) + list(WIDE_SIGNATURES.items()):
+            if other and not hasattr(lib, name):
+                continue  # an older build loaded for an A/B (tools/ab_libs.py, HOP_LIB)
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

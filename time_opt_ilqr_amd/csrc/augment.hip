@@ -21,7 +21,10 @@ constexpr int TPB = 256;
 // workgroup covers 256 / n steps (small n: long contiguous output runs)
 __host__ __device__ inline int steps_per_block(int n) { return TPB / n; }
 
-template <class T>
+// NMAX: the largest n the instantiation takes (the LDS copies of Q, _sym(Q), P):
+// 16 for the narrow entries, 32 for hop_augment_wide_f64 (n <= 31) -- one source, so
+// the wide blocks are built with the narrow builder's arithmetic
+template <class T, int NMAX>
 __global__ __launch_bounds__(TPB) void augment_kernel(AugArgs<T> a) {
   const TrajArgs<T>& t = a.t;
   const int n = t.n, m = t.m, s = n + 1;
@@ -34,7 +37,7 @@ __global__ __launch_bounds__(TPB) void augment_kernel(AugArgs<T> a) {
   // per-step vectors, [step][state] with row length n (KS * n <= 256)
   __shared__ T e0[TPB], e1[TPB], qe[TPB], pe[TPB], at[TPB];
   __shared__ T eqe[TPB], epe[TPB];
-  __shared__ T sQ[16 * 16], sQs[16 * 16], sP[16 * 16];
+  __shared__ T sQ[NMAX * NMAX], sQs[NMAX * NMAX], sP[NMAX * NMAX];
 
   const T* xg = t.xg + b * t.xg_bs;
   const T* ur = t.u_ref + b * t.ur_bs;
@@ -164,16 +167,25 @@ __global__ __launch_bounds__(TPB) void augment_kernel(AugArgs<T> a) {
 
 }  // namespace aug
 
-template <class T>
-hipError_t dispatch_augment(const AugArgs<T>& a, hipStream_t stream) {
+template <class T, int NMAX>
+hipError_t launch_augment(const AugArgs<T>& a, hipStream_t stream) {
   const int ksb = aug::steps_per_block(a.t.n);
   const long long nchunk = (a.nbuild + ksb - 1) / ksb;
   const long long blocks = a.batch * nchunk;
   if (blocks <= 0) return hipSuccess;
   if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(aug::augment_kernel<T>, dim3((unsigned)blocks), dim3(aug::TPB), 0, stream,
-                     a);
+  hipLaunchKernelGGL((aug::augment_kernel<T, NMAX>), dim3((unsigned)blocks), dim3(aug::TPB), 0,
+                     stream, a);
   return hipGetLastError();
+}
+
+template <class T>
+hipError_t dispatch_augment(const AugArgs<T>& a, hipStream_t stream) {
+  return launch_augment<T, 16>(a, stream);
+}
+// n <= 31 (include/hop_wide.h)
+hipError_t dispatch_augment_wide(const AugArgs<double>& a, hipStream_t stream) {
+  return launch_augment<double, 32>(a, stream);
 }
 
 template hipError_t dispatch_augment<double>(const AugArgs<double>&, hipStream_t);

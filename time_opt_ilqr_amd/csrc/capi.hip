@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "../../include/hop.h"
+#include "../../include/hop_wide.h"
 #include "hop_device.hpp"
 #include "hop_kernels.hpp"
 #include "dynamics.hpp"
@@ -33,6 +34,15 @@ int hip_status(hipError_t e) {
   snprintf(g_err, sizeof(g_err), "HIP error %d: %s", (int)e, hipGetErrorString(e));
   return HOP_E_HIP;
 }
+
+}  // namespace
+
+namespace hop {
+int set_error(int code, const char* msg) { return fail(code, msg); }
+int set_hip_status(hipError_t e) { return hip_status(e); }
+}  // namespace hop
+
+namespace {
 
 // first minimiser of J[t_min-1 .. t_max-1]; NaN wins (np.argmin semantics)
 template <class T>
@@ -249,9 +259,13 @@ int jcurve_entry(const T* A, const T* Bm, const T* X, const T* U, const T* xg, i
 
 // ---- trajectory form (augmented.py:10-87 on the device) -------------------
 template <class T>
-int traj_check(const hop::TrajArgs<T>& t, int64_t batch, int32_t n_alloc, int32_t n_build) {
+int traj_check(const hop::TrajArgs<T>& t, int64_t batch, int32_t n_alloc, int32_t n_build,
+               bool wide = false) {
   if (batch < 0) return fail(HOP_E_ARG, "batch < 0");
-  if (t.n < 1 || t.n + 1 > HOP_MAX_DIM) return fail(HOP_E_SIZE, "n must be in [1, 15]");
+  if (wide && (t.n < 1 || t.n + 1 > HOP_WIDE_MAX_DIM))
+    return fail(HOP_E_SIZE, "n must be in [1, 31]");
+  if (!wide && (t.n < 1 || t.n + 1 > HOP_MAX_DIM))
+    return fail(HOP_E_SIZE, "n must be in [1, 15]");
   if (t.m < 1 || t.m > HOP_MAX_DIM) return fail(HOP_E_SIZE, "m must be in [1, 16]");
   if (n_build > n_alloc) return fail(HOP_E_ARG, "n_use > n_alloc (reference IndexError)");
   // an empty batch (an empty shard) passes NULL data pointers: nothing is read
@@ -306,14 +320,18 @@ int64_t traj_ws_bytes(int64_t batch, int32_t n_use, int32_t n, int32_t m, int32_
 
 template <class T>
 int augment_entry(const hop::TrajArgs<T>& t, int64_t batch, int32_t n_alloc, int32_t n_build,
-                  T* A_aug, T* B_aug, T* Q_aug, T* QT_aug, T* z0, void* stream) {
-  const int rc = traj_check(t, batch, n_alloc, n_build);
+                  T* A_aug, T* B_aug, T* Q_aug, T* QT_aug, T* z0, void* stream,
+                  bool wide = false) {
+  const int rc = traj_check(t, batch, n_alloc, n_build, wide);
   if (rc != HOP_OK) return rc;
   if (batch == 0 || n_build <= 0) return HOP_OK;
   if (!A_aug || !B_aug || !Q_aug || !QT_aug) return fail(HOP_E_ARG, "null output pointer");
   hop::AugArgs<T> a{};
   a.t = t; a.batch = batch; a.nalloc = n_alloc; a.nbuild = n_build;
   a.A_aug = A_aug; a.B_aug = B_aug; a.Q_aug = Q_aug; a.QT_aug = QT_aug; a.z0 = z0;
+  if constexpr (sizeof(T) == 8) {
+    if (wide) return hip_status(hop::dispatch_augment_wide(a, (hipStream_t)stream));
+  }
   return hip_status(hop::dispatch_augment<T>(a, (hipStream_t)stream));
 }
 
@@ -537,6 +555,19 @@ int hop_augment_f64(const double* A, const double* Bm, const double* a_res, cons
       traj_args<double>(A, Bm, a_res, X, U, xg, xg_bs, u_ref, ur_bs, Q, q_bs, P, p_bs, w, w_bs,
                         qxx_extra, qx_extra, c_extra, wrap_mask, q_reg, rho_reg, n, m),
       batch, n_alloc, n_build, A_aug, B_aug, Q_aug, QT_aug, z0, stream);
+}
+int hop_augment_wide_f64(const double* A, const double* Bm, const double* a_res, const double* X,
+                         const double* U, const double* xg, int64_t xg_bs, const double* u_ref,
+                         int64_t ur_bs, const double* Q, int64_t q_bs, const double* P,
+                         int64_t p_bs, const double* w, int64_t w_bs, const double* qxx_extra,
+                         const double* qx_extra, const double* c_extra, uint32_t wrap_mask,
+                         double q_reg, double rho_reg, int64_t batch, int32_t n_alloc,
+                         int32_t n_build, int32_t n, int32_t m, double* A_aug, double* B_aug,
+                         double* Q_aug, double* QT_aug, double* z0, void* stream) {
+  return augment_entry<double>(
+      traj_args<double>(A, Bm, a_res, X, U, xg, xg_bs, u_ref, ur_bs, Q, q_bs, P, p_bs, w, w_bs,
+                        qxx_extra, qx_extra, c_extra, wrap_mask, q_reg, rho_reg, n, m),
+      batch, n_alloc, n_build, A_aug, B_aug, Q_aug, QT_aug, z0, stream, true);
 }
 int hop_augment_f32(const float* A, const float* Bm, const float* a_res, const float* X,
                     const float* U, const float* xg, int64_t xg_bs, const float* u_ref,

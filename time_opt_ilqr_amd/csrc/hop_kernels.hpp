@@ -39,6 +39,10 @@ inline long long cu_count(hipStream_t stream) {
   cached[dev].store(cus, std::memory_order_relaxed);
   return cus;
 }
+// hop_last_error's message and return code for entries outside capi.hip (lft_wide.hip,
+// riccati_wide.hip)
+int set_error(int code, const char* msg);
+int set_hip_status(hipError_t e);
 #ifdef HOP_DEV
 inline constexpr bool kDevBuild = true;
 #else
@@ -263,6 +267,11 @@ template <class T>
 hipError_t dispatch_lft_small(const LftArgs<T>& a, hipStream_t stream);
 template <class T>
 hipError_t dispatch_augment(const AugArgs<T>& a, hipStream_t stream);
+// the wide fp64 path (include/hop_wide.h): s <= 32 sweep (lft_wide.hip), n <= 31 builder
+namespace wide {
+hipError_t dispatch_lft_wide(const LftArgs<double>& a, hipStream_t stream);
+}
+hipError_t dispatch_augment_wide(const AugArgs<double>& a, hipStream_t stream);
 template <class T>
 hipError_t dispatch_riccati(const RiccatiArgs<T>& a, hipStream_t stream);
 // exact-size fp64 Riccati kernel (n = 12, m = 4; riccati_fast.hip), NotSupported otherwise

@@ -169,9 +169,15 @@ def propagate(A, B, Q, R, z0, QT, *, n_use: Optional[int] = None, r_is_inverse: 
                [m, m] | [Bn or 1, m, m] | [Bn or 1, N, m, m] (per step)
     n_use    : T_use (default N).  t_min/t_max: fuse the argmin (solver.py:522).
     A, B, Q, QT may instead all be ``Tile64`` (s <= 5 shapes; see to_tile64).
+    s > 16 (up to 32) runs the wide fp64 kernel: float64 batch-major blocks only, and
+    R must be R^-1 (shared, per problem or per step; invert a raw R with
+    ``utils.chol_inv`` first).
     """
     torch = _torch()
     if isinstance(A, Tile64):
+        if A.rows > _lib.MAX_DIM:
+            raise ValueError("wide shapes (s > 16) take batch-major float64 blocks, not Tile64; "
+                             "R must be R^-1 (utils.chol_inv)")
         if return_efg or return_prefix:
             raise ValueError("tile64 sweep: no debug outputs")
         return _propagate_tile64(A, B, Q, R, z0, QT, n_use, r_is_inverse, max_tries, t_min,
@@ -188,6 +194,10 @@ def propagate(A, B, Q, R, z0, QT, *, n_use: Optional[int] = None, r_is_inverse: 
         raise ValueError(f"A must be [B, N, s, s], got {tuple(A.shape)}")
     Bn, N, s, _ = A.shape
     m = B.shape[-1]
+    wide = s > _lib.MAX_DIM
+    if wide and (dt != torch.float64 or not r_is_inverse):
+        raise ValueError("wide shapes (s > 16) are float64 only and take R^-1 "
+                         "(r_is_inverse=True): invert a raw R with utils.chol_inv first")
     if tuple(B.shape) != (Bn, N, s, m):
         raise ValueError(f"B must be [B, N, s, m], got {tuple(B.shape)}")
     for name, t in (("Q", Q), ("QT", QT)):
@@ -223,7 +233,8 @@ def propagate(A, B, Q, R, z0, QT, *, n_use: Optional[int] = None, r_is_inverse: 
     js = torch.empty((Bn,), dtype=dt, device=dev) if fuse else None
     efg = torch.empty((Bn, n_eff, 3, s, s), dtype=dt, device=dev) if return_efg else None
     pre = torch.empty((Bn, n_eff, 3, s, s), dtype=dt, device=dev) if return_prefix else None
-    rc = _fn("hop_lft_sweep", dt)(
+    fn = _lib.load().hop_lft_sweep_wide_f64 if wide else _fn("hop_lft_sweep", dt)
+    rc = fn(
         _lib.ptr(A), _lib.ptr(B), _lib.ptr(Q), _lib.ptr(R), r_bs, r_ks, 1 if r_is_inverse else 0,
         _lib.ptr(QT), _lib.ptr(z0), z_bs, Bn, N, n_use, s, m, int(max_tries),
         int(t_min) if fuse else 0, int(t_max) if fuse else 0,
@@ -421,6 +432,10 @@ def riccati(A, Bm, X, U, xg, u_ref, Q, R, Qf, horizon, lm, *, mode: int = 0,
     A = _dev(A, "A", dt)
     dev = A.device
     Bn, N, n, _ = A.shape
+    wide = n > _lib.MAX_DIM  # n <= 31: hop_riccati_wide_f64 (fp64 only)
+    if wide and (dt != torch.float64 or legacy):
+        raise ValueError("wide shapes (n > 16) are float64 only, without the legacy passes "
+                         "(R stays raw here; the wide sweep takes utils.chol_inv(R))")
     Bm = _dev(Bm, "Bm", dt, dev)
     m = Bm.shape[-1]
     X = _dev(X, "X", dt, dev)
@@ -460,7 +475,8 @@ def riccati(A, Bm, X, U, xg, u_ref, Q, R, Qf, horizon, lm, *, mode: int = 0,
             *ins, _lib.ptr(horizon), _lib.ptr(lm), float(w_stage), wrap_mask(wrap_idx, n),
             int(mode), Bn, N, n, m, *outs)
     else:
-        rc = _fn("hop_riccati", dt)(
+        fn = _lib.load().hop_riccati_wide_f64 if wide else _fn("hop_riccati", dt)
+        rc = fn(
             *ins, _lib.ptr(ex[0]), _lib.ptr(ex[1]), _lib.ptr(ex[2]), _lib.ptr(horizon),
             _lib.ptr(lm), float(w_stage), wrap_mask(wrap_idx, n), int(mode), int(reg_max_tries),
             Bn, N, n, m, *outs)
@@ -602,12 +618,17 @@ def augment(A, Bm, a_res, X, U, xg, u_ref, Q, P, w, *, wrap_idx=None,
     if nb > N:
         raise IndexError(f"n_build={nb} exceeds the {N} stages supplied")
     s = n + 1
+    wide = s > _lib.MAX_DIM  # n >= 16: hop_augment_wide_f64 (fp64 only)
+    if wide and dt != torch.float64:
+        raise ValueError("wide shapes (n >= 16) are float64 only (the wide sweep takes "
+                         "R^-1 = utils.chol_inv(R))")
     out = AugmentedBlocks(torch.empty((Bn, nb, s, s), dtype=dt, device=dev),
                           torch.empty((Bn, nb, s, m), dtype=dt, device=dev),
                           torch.empty((Bn, nb, s, s), dtype=dt, device=dev),
                           torch.empty((Bn, nb, s, s), dtype=dt, device=dev),
                           torch.empty((s,), dtype=dt, device=dev))
-    rc = _fn("hop_augment", dt)(*args, Bn, N, nb, n, m, _lib.ptr(out.A), _lib.ptr(out.B),
+    fn = _lib.load().hop_augment_wide_f64 if wide else _fn("hop_augment", dt)
+    rc = fn(*args, Bn, N, nb, n, m, _lib.ptr(out.A), _lib.ptr(out.B),
                                 _lib.ptr(out.Q), _lib.ptr(out.QT), _lib.ptr(out.z0),
                                 _lib.stream_handle(dev))
     _lib.check(rc)
@@ -628,6 +649,9 @@ def propagate_traj(A, Bm, a_res, X, U, xg, u_ref, Q, R_inv, P, w, *, wrap_idx=No
     """
     torch = _torch()
     if isinstance(A, Tile64):
+        if A.rows >= _lib.MAX_DIM:
+            raise ValueError("wide shapes (n >= 16) take batch-major float64 tensors, not "
+                             "Tile64; R_inv = utils.chol_inv(R)")
         if any(t is not None for t in (qxx_extra, qx_extra, c_extra)):
             raise ValueError("tile64 trajectory form: no extra_stage_cost")
         return _propagate_traj_tile64(A, Bm, a_res, X, U, xg, u_ref, Q, R_inv, P, w, wrap_idx,
@@ -642,6 +666,15 @@ def propagate_traj(A, Bm, a_res, X, U, xg, u_ref, Q, R_inv, P, w, *, wrap_idx=No
     n_use = N if n_use is None else int(n_use)
     if n_use > N:
         raise IndexError(f"T_use={n_use} exceeds the {N} stages supplied")
+    if n + 1 > _lib.MAX_DIM:
+        # wide shapes: the wide builder into torch tensors (the workspace), then the
+        # wide sweep; both validate dtype and R_inv
+        del keep
+        blk = augment(A, Bm, a_res, X, U, xg, u_ref, Q, P, w, wrap_idx=wrap_idx,
+                      n_build=max(n_use, 0), q_reg=q_reg, rho_reg=rho_reg, qxx_extra=qxx_extra,
+                      qx_extra=qx_extra, c_extra=c_extra)
+        return propagate(blk.A, blk.B, blk.Q, R_inv, blk.z0, blk.QT, n_use=n_use,
+                         max_tries=max_tries, t_min=t_min, t_max=t_max)
     n_eff = max(n_use, 0)
     J = torch.empty((Bn, n_eff), dtype=dt, device=dev)
     # every sweep kernel writes the status of each problem it runs

@@ -75,8 +75,14 @@ def propagator_all_Jt_aug(A_aug, B_aug, Q_aug, R_list, z0, QT_aug_list,
     if R_inv_cached is None:
         if len(R_list) < N:
             raise IndexError("list index out of range")
-        R = np.stack([np.asarray(r, dtype=float) for r in R_list[:N]])[None]
-        r_inv = False
+        if A.shape[-1] > _lib.MAX_DIM:
+            # the wide sweep (s > 16) takes R^-1 only: the reference's own per-step
+            # chol_inv(R_k) (horizon_selection.py:52), on the host
+            R = np.stack([chol_inv(np.asarray(r, dtype=float)) for r in R_list[:N]])[None]
+            r_inv = True
+        else:
+            R = np.stack([np.asarray(r, dtype=float) for r in R_list[:N]])[None]
+            r_inv = False
     else:
         R = np.asarray(R_inv_cached, dtype=float)
         r_inv = True

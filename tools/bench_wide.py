@@ -1,0 +1,164 @@
+"""Timings of the wide fp64 path (include/hop_wide.h) on one GPU, device events, warmed.
+
+    python tools/bench_wide.py [--batch 4096] [--N 100] [--rounds 5] [--iters 3]
+                               [--out profiles/wide_sweep.jsonl]
+
+Writes one JSON line per measurement:
+  * "wide_vs_generic": hop_lft_sweep_wide_f64 at s = 16, m = 4 against the narrow
+    reference-association kernel (HOP_OPT_FORCE_GENERIC) on the same inputs, the two
+    alternated round by round in this process (never rank timings from different
+    processes); J compared before timing.
+  * "wide_sweep": ms per sweep at s = 17, 24, 32 with m = 4 and m = 8.
+  * "wide_riccati": hop_riccati_wide_f64 mode 0 at n = 31, m = 8, horizon N.
+Each line carries the FLOP and byte counts of bench.py's roofline (lft_flops /
+lft_bytes / riccati_flops), the achieved TFLOP/s and GB/s, the least time either bound
+allows and which one it is, and the fraction of the fp64 peak.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def _timed(fn, rounds, iters):
+    import torch
+    ms = []
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / iters)
+    return ms
+
+
+def _roof(flops, nbytes, batch, ms, bench):
+    t = ms * 1e-3
+    t_flop = flops * batch / (bench.PEAK_F64_TFLOPS * 1e12)
+    t_byte = nbytes * batch / (bench.PEAK_HBM_GBS * 1e9)
+    return dict(flops_per_problem=flops, bytes_per_problem=nbytes,
+                tflops=flops * batch / t / 1e12, gbs=nbytes * batch / t / 1e9,
+                frac_fp64_peak=flops * batch / t / 1e12 / bench.PEAK_F64_TFLOPS,
+                bound="fp64" if t_flop >= t_byte else "hbm",
+                least_ms=max(t_flop, t_byte) * 1e3, frac_of_bound=max(t_flop, t_byte) / t)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--N", type=int, default=100)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "wide_sweep.jsonl"))
+    args = ap.parse_args()
+    import torch
+    import bench
+    from time_opt_ilqr_amd import _lib, engine, synth
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_wide.py needs a HIP device (no CPU fallback)")
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    Bn, N = args.batch, args.N
+    rows = []
+
+    def wide_call(A, Bm, Q, Ri, z0, QT, s, m):
+        J = torch.empty((Bn, N), dtype=torch.float64, device=dev)
+        st = torch.empty((Bn,), dtype=torch.int32, device=dev)
+        r_bs = 0 if Ri.dim() == 2 else m * m
+
+        def fn():
+            _lib.check(lib.hop_lft_sweep_wide_f64(
+                _lib.ptr(A), _lib.ptr(Bm), _lib.ptr(Q), _lib.ptr(Ri), r_bs, 0, 1, _lib.ptr(QT),
+                _lib.ptr(z0), 0, Bn, N, N, s, m, 8, 0, 0, _lib.ptr(J), _lib.ptr(st), None, None,
+                None, None, _lib.stream_handle(dev)))
+        return fn, J, st
+
+    # ---- wide against the narrow reference-association kernel at s = 16
+    s, m = 16, 4
+    A, Bm, Q, Ri, z0, QT = synth.device_batch(Bn, s, m, N, seed=5, device=dev)
+    wfn, Jw, stw = wide_call(A, Bm, Q, Ri, z0, QT, s, m)
+
+    def gfn():
+        with _lib.options(force_generic=True):
+            return engine.propagate(A, Bm, Q, Ri, z0, QT)
+    wfn()
+    ref = gfn()
+    torch.cuda.synchronize()
+    rel = float(((Jw - ref.J).abs() / ref.J.abs()).max())
+    assert int(stw.abs().sum()) == 0 and int(ref.status.abs().sum()) == 0
+    tw, tg = [], []
+    for rnd in range(args.rounds):  # alternate, order flipped every round
+        for which in ((0, 1) if rnd % 2 == 0 else (1, 0)):
+            (tw if which == 0 else tg).extend(_timed(wfn if which == 0 else gfn, 1, args.iters))
+    mw, mg = statistics.median(tw), statistics.median(tg)
+    rows.append(dict(kind="wide_vs_generic", s=s, m=m, N=N, batch=Bn, max_rel_J=rel,
+                     wide_ms=mw, wide_ms_all=tw, generic_ms=mg, generic_ms_all=tg,
+                     ratio_wide_over_generic=mw / mg,
+                     wide=_roof(bench.lft_flops(N, s, m), bench.lft_bytes(N, s, m), Bn, mw, bench),
+                     generic=_roof(bench.lft_flops(N, s, m), bench.lft_bytes(N, s, m), Bn, mg,
+                                   bench)))
+    print(json.dumps(rows[-1]), flush=True)
+    del A, Bm, Q, QT
+
+    # ---- wide shapes
+    for s, m in ((17, 4), (17, 8), (24, 4), (24, 8), (32, 4), (32, 8)):
+        A, Bm, Q, Ri, z0, QT = synth.device_batch(Bn, s, m, N, seed=5, device=dev)
+        fn, J, st = wide_call(A, Bm, Q, Ri, z0, QT, s, m)
+        fn()
+        torch.cuda.synchronize()
+        assert int(st.abs().sum()) == 0 and bool(torch.isfinite(J).all())
+        ms = _timed(fn, args.rounds, args.iters)
+        med = statistics.median(ms)
+        rows.append(dict(kind="wide_sweep", s=s, m=m, N=N, batch=Bn, ms=med, ms_all=ms,
+                         **_roof(bench.lft_flops(N, s, m), bench.lft_bytes(N, s, m), Bn, med,
+                                 bench)))
+        print(json.dumps(rows[-1]), flush=True)
+        del A, Bm, Q, QT, J
+
+    # ---- wide Riccati, mode 0, n = 31
+    n, m = 31, 8
+    g = torch.Generator(device="cpu").manual_seed(11)
+    rnd = lambda *sh: torch.randn(*sh, generator=g, dtype=torch.float64)  # noqa: E731
+    A = (torch.eye(n, dtype=torch.float64) + 0.05 * rnd(Bn, N, n, n)).to(dev)
+    Bm = (0.1 * rnd(Bn, N, n, m)).to(dev)
+    X = (0.5 * rnd(Bn, N + 1, n)).to(dev)
+    U = (0.1 * rnd(Bn, N, m)).to(dev)
+    xg, ur = torch.zeros(n, dtype=torch.float64, device=dev), torch.zeros(m, dtype=torch.float64,
+                                                                          device=dev)
+    Qc = torch.eye(n, dtype=torch.float64, device=dev)
+    Rc = 0.5 * torch.eye(m, dtype=torch.float64, device=dev)
+    Qf = 10.0 * torch.eye(n, dtype=torch.float64, device=dev)
+    T = torch.full((Bn,), N, dtype=torch.int32, device=dev)
+
+    def rfn():
+        return engine.riccati(A, Bm, X, U, xg, ur, Qc, Rc, Qf, T, 1e-3, mode=0)
+    r = rfn()
+    torch.cuda.synchronize()
+    assert int(r.status.abs().sum()) == 0
+    ms = _timed(rfn, args.rounds, args.iters)
+    med = statistics.median(ms)
+    rb = 8 * (N * (n * n + n * m + m + m * n + m) + (N + 1) * n)  # A, B, U in; K, k out; X
+    rows.append(dict(kind="wide_riccati", mode=0, n=n, m=m, N=N, batch=Bn, ms=med, ms_all=ms,
+                     **_roof(bench.riccati_flops(n, m, N, 0), rb, Bn, med, bench)))
+    print(json.dumps(rows[-1]), flush=True)
+
+    # rows of other kinds (counter runs, the parent benchmark, the resource table) stay
+    keep = []
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            keep = [r for r in map(json.loads, filter(str.strip, f))
+                    if r.get("kind") not in ("wide_vs_generic", "wide_sweep", "wide_riccati")]
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        for r in rows + keep:
+            f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
