@@ -121,6 +121,11 @@ WIDE_SIGNATURES = {
     "hop_riccati_wide_f64": (C.c_int, _RIC64),
 }
 
+# include/hop_wide_jcurve.h (the brute-force J curve for n <= 31); bound beside the others
+WIDE_JCURVE_SIGNATURES = {
+    "hop_bruteforce_jcurve_wide_f64": (C.c_int, _JC64),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -146,7 +151,8 @@ def load(path: str | None = None):
         import torch  # noqa: F401
         lib = C.CDLL(p)
         other = path is not None or "HOP_LIB" in os.environ
-        for name, (res, args) in list(SIGNATURES.items()) + list(WIDE_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(WIDE_SIGNATURES.items())
+                                  + list(WIDE_JCURVE_SIGNATURES.items())):
             if other and not hasattr(lib, name):
                 continue  # an older build loaded for an A/B (tools/ab_libs.py, HOP_LIB)
             fn = getattr(lib, name)

@@ -56,7 +56,7 @@ def _digest():
     for name in SOURCES + DEV_SOURCES + HEADERS:
         with open(os.path.join(CSRC, name), "rb") as f:
             h.update(f.read())
-    for name in ("hop.h", "hop_wide.h"):
+    for name in ("hop.h", "hop_wide.h", "hop_wide_jcurve.h"):
         with open(os.path.join(REPO, "include", name), "rb") as f:
             h.update(f.read())
     if ELIDE:  # the device code is what tools/nop_elide.py leaves of the compiler's

@@ -142,7 +142,8 @@ struct RiccatiArgs {
   // J-curve form (hop_bruteforce_jcurve_*, solver.py:293-358): when jc_J is set, the
   // generic J-curve kernel's workgroup x runs problem block x / jc_tmax at horizon
   // L = jc_tmax - x % jc_tmax, the exact-size kernel's workgroup x the pair of
-  // horizons jc_tmax - h and h + 1 of block x / P (h = x % P, P = ceil(jc_tmax / 2));
+  // horizons jc_tmax - h and h + 1 of block x / P (h = x % P, P = ceil(jc_tmax / 2)),
+  // the wide kernel's wave g problem g / jc_tmax at horizon jc_tmax - g % jc_tmax;
   // one horizon per wave at a time, a block's horizons adjacent, longest first;
   // lm is the scalar lm_value, no K / k / V is stored and each (problem, horizon)
   // writes J[b][L-1] = V_0 and its status to jc_status[b][L-1]

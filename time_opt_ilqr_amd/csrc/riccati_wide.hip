@@ -11,6 +11,7 @@
 #include "hop_wide_device.hpp"
 #include "hop_kernels.hpp"
 #include "../../include/hop_wide.h"
+#include "../../include/hop_wide_jcurve.h"
 
 namespace hop {
 namespace wide {
@@ -133,12 +134,22 @@ __device__ __forceinline__ bool spd_inverse_nofallback(double (&r)[MR], const Ct
   return good;
 }
 
-template <int HR, int MODE>
+// JC: the J-curve form (hop_bruteforce_jcurve_wide_f64, solver.py:293-358), on the mode-1
+// step.  Wave g of the launch runs problem g / jc_tmax at horizon jc_tmax - g % jc_tmax,
+// so a problem's horizons are adjacent and longest first and the re-reads of its A, B,
+// X, U meet in the caches (riccati.hip's riccati_jcurve_kernel has that order per
+// workgroup).  lm is the scalar lm_value, nothing of K, k, V is stored, V_0 and the status
+// go to jc_J / jc_status[prob][L - 1], and the failure rules are the brute-force curve's.
+// Every JC branch is a compile-time one: the single-pass instantiations compile to what
+// they were without it.
+template <int HR, int MODE, bool JC = false>
 __global__ __launch_bounds__(64 * kWavesPerBlockW) void riccati_wide_kernel(RiccatiArgs<double> a) {
   __shared__ __attribute__((aligned(16))) double smem[kWavesPerBlockW * kLdsWave];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const long long prob = (long long)blockIdx.x * kWavesPerBlockW + wv;
-  if (prob >= a.batch) return;  // wave-uniform
+  const long long wave = (long long)blockIdx.x * kWavesPerBlockW + wv;
+  if (wave >= (JC ? a.batch * a.jc_tmax : a.batch)) return;  // wave-uniform
+  const long long prob = JC ? wave / a.jc_tmax : wave;
+  const int jl = JC ? a.jc_tmax - (int)(wave - prob * a.jc_tmax) : 0;
   const int n = a.n, m = a.m, NA = a.nalloc;
   Ctx w;
   w.L = smem + wv * kLdsWave;
@@ -163,8 +174,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlockW) void riccati_wide_kernel(Ricc
   const double* Qp = a.Q + prob * a.q_bstride;
   const double* Rp = a.R + prob * a.r_bstride;
   const double* Qfp = a.Qf + prob * a.qf_bstride;
-  const int L = a.horizon[prob];
-  const double lam0 = a.lm[prob];
+  const int L = JC ? jl : a.horizon[prob];
+  const double lam0 = JC ? a.lm_value : a.lm[prob];
 
   // loop-invariant cost blocks: Q and R by columns and transposed
   double qcol[HR], qT[HR], rcol[MR], rT[MR];
@@ -196,7 +207,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlockW) void riccati_wide_kernel(Ricc
     vx = dot_col(qfT, eT, w);
     v0 = 0.5 * vec_sum((c < n) ? eT * vx : 0.0);
     symmetrize(Vxx, w);
-    if (alive) {
+    if (!JC && alive) {
       if (a.Vxx) store_cols(a.Vxx + (prob * (NA + 1) + L) * nn, n, n, w, Vxx);
       if (a.Vx && c < n && w.h == 0) a.Vx[prob * (NA + 1) * n + (long long)L * n + c] = vx;
       if (a.V0 && lane == 0) a.V0[prob * (NA + 1) + L] = v0;
@@ -208,7 +219,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlockW) void riccati_wide_kernel(Ricc
     double e = (c < n) ? Xp[(long long)i * n + (c < n ? c : 0)] - xg_c : 0.0;
     if (wrap_c) e = wrap_angle(e);
     const double du = (c < m) ? Up[(long long)i * m + (c < m ? c : 0)] - ur_c : 0.0;
-    const bool bad = any_lane(!(finite_val(e) && finite_val(du)));
+    // the brute-force curve (solver.py:326-356) checks nothing itself: only its
+    // chol_solve raises, so a non-finite e at t = 0 only feeds V_0 (inf / NaN in J)
+    const bool e_ok = (JC && i == 0) || finite_val(e);
+    const bool bad = any_lane(!(e_ok && finite_val(du)));
 
     // lx = Q e (+ cx), lu = R du, l0
     double lx = dot_col(qT, e, w);
@@ -331,9 +345,18 @@ __global__ __launch_bounds__(64 * kWavesPerBlockW) void riccati_wide_kernel(Ricc
     vxn = (c < n) ? vxn : 0.0;
     mask2(Vn, w, n, n);
     symmetrize(Vn, w);
-    bool vbad = !finite_val(vxn) || !finite_val(v0n);
+    // value_expansions (horizon_selection.py:209-210) raises on any non-finite V.  The
+    // brute-force curve raises only through the next step's chol_solve: a non-finite
+    // Vxx / Vx fails there, a non-finite V_0 never does, and at t = 0 nothing follows,
+    // so only chol_solve(Quu_reg, Qux) itself can raise (Qux).
+    bool vbad = !finite_val(vxn) || (!JC && !finite_val(v0n));
 #pragma unroll
     for (int r = 0; r < HR; ++r) vbad = vbad || !finite_val(Vn[r]);
+    if (JC && i == 0) {
+      vbad = false;
+#pragma unroll
+      for (int r = 0; r < MR; ++r) vbad = vbad || !finite_val(Qux[r]);
+    }
     const bool vfail = any_lane(vbad);
 
     if (fail_row || vfail) {
@@ -345,14 +368,24 @@ __global__ __launch_bounds__(64 * kWavesPerBlockW) void riccati_wide_kernel(Ricc
       for (int r = 0; r < HR; ++r) Vxx[r] = Vn[r];
       vx = vxn;
       v0 = v0n;
-      store_cols(a.K + (prob * NA + i) * (long long)m * n, m, n, w, K);
-      if (c < m && w.h == 0) a.k[(prob * NA + i) * m + c] = kv;
-      if (a.Vxx) store_cols(a.Vxx + (prob * (NA + 1) + i) * nn, n, n, w, Vn);
-      if (a.Vx && c < n && w.h == 0) a.Vx[prob * (NA + 1) * n + (long long)i * n + c] = vxn;
-      if (a.V0 && lane == 0) a.V0[prob * (NA + 1) + i] = v0n;
+      if constexpr (!JC) {
+        store_cols(a.K + (prob * NA + i) * (long long)m * n, m, n, w, K);
+        if (c < m && w.h == 0) a.k[(prob * NA + i) * m + c] = kv;
+        if (a.Vxx) store_cols(a.Vxx + (prob * (NA + 1) + i) * nn, n, n, w, Vn);
+        if (a.Vx && c < n && w.h == 0) a.Vx[prob * (NA + 1) * n + (long long)i * n + c] = vxn;
+        if (a.V0 && lane == 0) a.V0[prob * (NA + 1) + i] = v0n;
+      }
     }
   }
-  if (lane == 0) a.status[prob] = (int)st;
+  if constexpr (JC) {  // V_0 of this horizon's sweep (the reference raises on failure: NaN)
+    if (lane == 0) {
+      const long long o = prob * a.jc_tmax + (L - 1);
+      a.jc_J[o] = alive ? v0 : __builtin_nan("");
+      a.jc_status[o] = (int)st;
+    }
+  } else {
+    if (lane == 0) a.status[prob] = (int)st;
+  }
 }
 
 template <int HR>
@@ -362,6 +395,21 @@ hipError_t launch_riccati_wide(const RiccatiArgs<double>& a, hipStream_t stream)
   if (a.mode == 0) hipLaunchKernelGGL((riccati_wide_kernel<HR, 0>), grid, block, 0, stream, a);
   else hipLaunchKernelGGL((riccati_wide_kernel<HR, 1>), grid, block, 0, stream, a);
   return hipGetLastError();
+}
+
+template <int HR>
+hipError_t launch_riccati_wide_jcurve(const RiccatiArgs<double>& a, hipStream_t stream) {
+  const long long waves = a.batch * (long long)a.jc_tmax;
+  const long long blocks = (waves + kWavesPerBlockW - 1) / kWavesPerBlockW;
+  hipLaunchKernelGGL((riccati_wide_kernel<HR, 1, true>), dim3((unsigned)blocks),
+                     dim3(64 * kWavesPerBlockW), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t dispatch_riccati_wide_jcurve(const RiccatiArgs<double>& a, hipStream_t stream) {
+  if (a.n <= 16) return launch_riccati_wide_jcurve<8>(a, stream);
+  if (a.n <= 24) return launch_riccati_wide_jcurve<12>(a, stream);
+  return launch_riccati_wide_jcurve<16>(a, stream);
 }
 
 hipError_t dispatch_riccati_wide(const RiccatiArgs<double>& a, hipStream_t stream) {
@@ -410,6 +458,48 @@ int hop_riccati_wide_f64(const double* A, const double* Bm, const double* X, con
   a.reg_max_tries = reg_max_tries; a.max_tries = 8; a.wrap_mask = wrap_mask; a.w_stage = w_stage;
   a.K = K; a.k = k; a.Vxx = Vxx; a.Vx = Vx; a.V0 = V0; a.status = status;
   return hop::set_hip_status(hop::wide::dispatch_riccati_wide(a, (hipStream_t)stream));
+}
+
+int hop_bruteforce_jcurve_wide_f64(const double* A, const double* Bm, const double* X,
+                                   const double* U, const double* xg, int64_t xg_bs,
+                                   const double* u_ref, int64_t ur_bs, const double* Q,
+                                   int64_t q_bs, const double* R, int64_t r_bs, const double* Qf,
+                                   int64_t qf_bs, const double* qxx_extra, const double* qx_extra,
+                                   const double* c_extra, double lm_lambda, double w_stage,
+                                   uint32_t wrap_mask, int64_t batch, int32_t n_alloc, int32_t n,
+                                   int32_t m, int32_t t_max, double* J, int32_t* status,
+                                   void* stream) {
+  using hop::set_error;
+  if (batch < 0) return set_error(HOP_E_ARG, "batch < 0");
+  if (n < 1 || n > HOP_WIDE_MAX_DIM - 1) return set_error(HOP_E_SIZE, "n must be in [1, 31]");
+  if (m < 1 || m > HOP_MAX_DIM) return set_error(HOP_E_SIZE, "m must be in [1, 16]");
+  if (t_max < 1) return set_error(HOP_E_ARG, "t_max < 1");
+  // the reference slices A_list[:T] for T <= T_max (an IndexError past N)
+  if (t_max > n_alloc) return set_error(HOP_E_ARG, "t_max > n_alloc (reference IndexError)");
+  if ((wrap_mask >> n) != 0u) return set_error(HOP_E_ARG, "wrap_mask names a state >= n");
+  if (xg_bs < 0 || ur_bs < 0 || q_bs < 0 || r_bs < 0 || qf_bs < 0)
+    return set_error(HOP_E_ARG, "negative stride");
+  if (batch > 0 && (!A || !Bm || !X || !U || !xg || !u_ref || !Q || !R || !Qf || !J || !status))
+    return set_error(HOP_E_ARG, "null pointer");
+  // one wave64 per (problem, horizon), kWavesPerBlockW per workgroup: the dispatch limit
+  // is in work-items, so the workgroups times their 64 kWavesPerBlockW lanes fit 32 bits
+  constexpr long long kMaxWaves =
+      0xFFFFFFFFll / (64 * hop::wide::kWavesPerBlockW) * hop::wide::kWavesPerBlockW;
+  if (batch > kMaxWaves / t_max)
+    return set_error(HOP_E_SIZE, "batch * t_max too large for one launch");
+  if (batch == 0) return HOP_OK;
+  hop::RiccatiArgs<double> a;
+  a.A = A; a.Bm = Bm; a.X = X; a.U = U; a.xg = xg; a.u_ref = u_ref; a.Q = Q; a.R = R; a.Qf = Qf;
+  a.qxx_extra = qxx_extra; a.qx_extra = qx_extra; a.c_extra = c_extra;
+  a.horizon = nullptr; a.lm = nullptr;
+  a.xg_bstride = xg_bs; a.uref_bstride = ur_bs; a.q_bstride = q_bs; a.r_bstride = r_bs;
+  a.qf_bstride = qf_bs;
+  a.batch = batch; a.nalloc = n_alloc; a.n = n; a.m = m; a.mode = 1;
+  a.reg_max_tries = 1; a.max_tries = 8; a.wrap_mask = wrap_mask; a.w_stage = w_stage;
+  a.K = nullptr; a.k = nullptr; a.Vxx = nullptr; a.Vx = nullptr; a.V0 = nullptr;
+  a.status = nullptr;
+  a.jc_J = J; a.jc_status = status; a.jc_tmax = t_max; a.lm_value = lm_lambda;
+  return hop::set_hip_status(hop::wide::dispatch_riccati_wide_jcurve(a, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -234,7 +234,8 @@ def bruteforce_all_Jt_backward_expansion(A_list, B_list, X, U, xg, u_ref, Q, R, 
                                          T_max: int, *, lm_lambda: float = 1e-6, wrap_idx=None,
                                          extra_stage_cost=None) -> np.ndarray:
     """Exact quadratic-model J(T) curve: T_max independent Riccati sweeps of
-    lengths 1..T_max, run as ONE launch (hop_bruteforce_jcurve, grid y = horizon)."""
+    lengths 1..T_max, run as ONE launch (hop_bruteforce_jcurve, grid y = horizon; for
+    n > 16 hop_bruteforce_jcurve_wide_f64, one wave per horizon)."""
     T_max = int(T_max)
     X = np.asarray(X, dtype=float)
     U = np.asarray(U, dtype=float)
@@ -247,7 +248,8 @@ def bruteforce_all_Jt_backward_expansion(A_list, B_list, X, U, xg, u_ref, Q, R, 
     Bm = _to_dev(np.stack([np.asarray(b, dtype=float) for b in B_list[:T_max]])[None])
     qxx, qx, c0 = _extra_arrays(extra_stage_cost, X, U, T_max)
     dv = lambda a: None if a is None else _to_dev(a)  # noqa: E731
-    J, st = engine.bruteforce_jcurve(
+    jcurve = engine.bruteforce_jcurve_wide if n > _lib.MAX_DIM else engine.bruteforce_jcurve
+    J, st = jcurve(
         A, Bm, _to_dev(X[None, :T_max + 1]), _to_dev(U[None, :T_max]),
         _to_dev(np.asarray(xg, float)), _to_dev(np.atleast_1d(np.asarray(u_ref, float))),
         _to_dev(Q), _to_dev(np.atleast_2d(R)), _to_dev(as_terminal_weight(alpha, n)), T_max,

@@ -80,7 +80,8 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
 
     The select step is the LFT sweep of the augmented system (propagator) or the
     brute-force J curve of T_max value-expansion sweeps (bruteforce, solver.py:293-358,
-    one hop_bruteforce_jcurve launch); everything after it is shared.
+    one hop_bruteforce_jcurve launch, the wide entry's for n > 16); everything after it
+    is shared.
 
     x0 [n] or [B, n] (torch or NumPy); U_init [B, N, m] or None (u_ref tiled);
     xg/u_ref/Q/R shared or per problem; Qf = as_terminal_weight(alpha) [n, n];
@@ -229,9 +230,11 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
                                         t_min=T_min, t_max=T_max, **ex)
             T_star, sel_status, sel_J = sel.t_star, sel.status, sel.J
         else:  # solver.py:607-614: the J curve at lm_lambda = 1e-6, argmin over [T_min, T_max]
-            sel_J, st_T = engine.bruteforce_jcurve(lin.A, lin.B, s.X, s.U, xg_t, ur_t, Q_t, R_t,
-                                                   Qf_t, T_max, lm_lambda=1e-6, w_stage=w_f,
-                                                   wrap_idx=wrap_idx, **ex)
+            # by shape alone, the rule of engine.riccati: n > 16 runs the wide J curve
+            jcurve = (engine.bruteforce_jcurve_wide if n > _lib.MAX_DIM
+                      else engine.bruteforce_jcurve)
+            sel_J, st_T = jcurve(lin.A, lin.B, s.X, s.U, xg_t, ur_t, Q_t, R_t, Qf_t, T_max,
+                                 lm_lambda=1e-6, w_stage=w_f, wrap_idx=wrap_idx, **ex)
             T_star, _ = engine.select_horizon(sel_J, T_min, T_max)
             # the reference raises at the first failing horizon: any horizon's
             # failure bits make the problem's select status
