@@ -126,10 +126,6 @@ struct SchedCond : SchedLdlDma {
 #define HOP_COND_DMAI 0  // A/B builds (tools/exp_build.py): the DMA pieces inside the update
 #endif
 constexpr bool kCondDmai = HOP_COND_DMAI != 0;
-#ifndef HOP_FMA3
-#define HOP_FMA3 0  // A/B builds: the congruence query's row offsets as inline-asm v_fma_f64
-#endif
-constexpr bool kFma3 = HOP_FMA3 != 0;
 #ifndef HOP_COND_SWEEP2
 #define HOP_COND_SWEEP2 0  // A/B: the s = 13 kernel's two sweeps as one interleaved block
 #endif
@@ -2811,6 +2807,25 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
   constexpr bool WQ = has_wq<C>() && (has_ldspipe<C>() || has_smalls<C>()) && !TRAJ && !MF;
   const double kmask = c < S - 1 ? -KOFF : 0.0;     // P11^-1 - KOFF I on lanes < S-1
   const double e_last = c == S - 1 ? 1.0 : 0.0;
+  // The two s = 13 fp64 defaults shed per-step bookkeeping (same operations on the same
+  // values, bitwise the plain form):
+  //   FOLD  the step's pivot minima run through one register and its NaN probes are
+  //         kept, all tested once at the step's end (developer builds keep the
+  //         per-block tests for their reasons);
+  //   LEAN1 (the one-wave kernel; the packed kernel's 256 registers have no room for the
+  //         rows and measured no gain from the FMAs) the eps I rows built once and held
+  //         in registers, the query's row offsets as three-address FMAs.
+  constexpr bool LEAN = (std::is_same_v<C, SchedCondLSymL> || std::is_same_v<C, SchedCondLSymP>) &&
+                        S == 13 && MM == 4 && !F32;
+  constexpr bool FOLD = LEAN && !kDevBuild;
+  constexpr bool LEAN1 = LEAN && !has_pack<C>();
+  double epsr[LEAN1 ? S : 1];
+  if constexpr (LEAN1) {
+    static_for<S>([&](auto I) {
+      epsr[I] = sel_lane<I>(0.0, 1e-9);
+      asm("" : "+v"(epsr[I]));  // opaque: not rebuilt from the SGPR masks inside the loop
+    });
+  }
   const T* imQ = reinterpret_cast<const T*>(wbase + G::OFF_Q + g * G::IMGM);
   const T* imA = reinterpret_cast<const T*>(wbase + G::OFF_A + g * G::IMGM);
   const T* imT = reinterpret_cast<const T*>(wbase + G::OFF_QT + g * G::IMGM);
@@ -3061,6 +3076,8 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
     stamp(0);
     if (!QPIPE && k > 0 && valid && c == 0) a.J[prob * N + k - 1] = (T)jprev;
     double atil = 0.0;
+    // FOLD: the step's running pivot minimum and its NaN probes, tested once at its end
+    double fmin = 1.0, pNE = 0.0, pNX = 0.0, pU = 0.0, pS = 0.0;
     if constexpr (F32) {
     } else if constexpr (TRAJ) {
       const double* sX = reinterpret_cast<const double*>(wbase + G::OFF_VX) + g * 2 * G::CHX;
@@ -3151,7 +3168,7 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
       const unsigned aq[2] = {in ? lds_addr(imT) + 8u * c : zaddr,
                               in ? lds_addr(imT) + 8u * S * c : zaddr};
       double d1 = 1.0, d2 = 1.0;
-      SweepQSym<S>::run(NE, d1, o, aq);
+      SweepQSym<S>::run(NE, FOLD ? fmin : d1, o, aq);
       if constexpr (dstag<C>() == 2) {  // the Q and QT images are read: refill them now
         wave_sync();
         if (k + 1 < N)
@@ -3162,10 +3179,17 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
       double o2[2 * S + MM];
       const unsigned ab[3] = {in ? lds_addr(imA) + 8u * S * c : zaddr, lds_addr(imA) + 8u * c,
                               in ? lds_addr(imB) + 8u * MM * c : zaddr};
-      if constexpr (WQ) SweepQABP<S>::run(NX, d2, o2, ab);  // pivots 0 .. S-2 (the query)
+      // WQ: pivots 0 .. S-2 (the query)
+      if constexpr (WQ) SweepQABP<S>::run(NX, FOLD ? fmin : d2, o2, ab);
       else SweepQAB<S>::run(NX, d2, o2, ab);
-      bad = bad || !pivots_ok(NE, d1) || !pivots_ok(NX, d2);
-      flag(!pivots_ok(NE, d1) || !pivots_ok(NX, d2), 1, k + 1);
+      if constexpr (FOLD) {
+        // pivots_ok's NaN probes are lane 0's own entries; only lane 0 stores the status
+        pNE = NE[0];
+        pNX = NX[0];
+      } else {
+        bad = bad || !pivots_ok(NE, d1) || !pivots_ok(NX, d2);
+        flag(!pivots_ok(NE, d1) || !pivots_ok(NX, d2), 1, k + 1);
+      }
 #pragma unroll
       for (int j = 0; j < S; ++j) {
         at[j] = o2[j];
@@ -3327,12 +3351,16 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
           CondLdlO2R0D<S>::run(r, Ht, X, dmin, q);
         }
       } else if constexpr (has_sym2<C>() && has_newt<C>()) CondLdl2<S>::run(r, Ht, X, dmin);
-      else if constexpr (has_sym2<C>()) CondLdlO2R0<S>::run(r, Ht, X, dmin);
+      else if constexpr (has_sym2<C>()) CondLdlO2R0<S>::run(r, Ht, X, FOLD ? fmin : dmin);
       else if constexpr (has_newt<C>()) CondLdlO1R1<S>::run(r, Ht, X, dmin);
       else CondLdl<S>::run(r, Ht, X, dmin);
       const double x = bcast<S - 1>(r[S - 1]);
-      bad = bad || !(dmin > 0.0) || (x != x);
-      flag(!(dmin > 0.0) || (x != x), 4, k + 1);
+      if constexpr (FOLD) {
+        pU = x;
+      } else {
+        bad = bad || !(dmin > 0.0) || (x != x);
+        flag(!(dmin > 0.0) || (x != x), 4, k + 1);
+      }
     }
     if (dma_late) {  // DSTAG 1: the odd waves' pieces, half a step after the even waves'
       wave_sync();
@@ -3428,7 +3456,10 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
       for (int i = 0; i < S; ++i) Tm[i] = X[i] * e_s;
       double (&atS)[S] = reinterpret_cast<double (&)[S]>(at);
       gxy<C, false, S, S>(Tm, Xs, atS);
-      static_for<S>([&](auto I) { X[I] = sel_lane<I>(0.0, 1e-9); });
+      static_for<S>([&](auto I) {
+        if constexpr (LEAN1) X[I] = epsr[I];
+        else X[I] = sel_lane<I>(0.0, 1e-9);
+      });
       if constexpr (has_arow<C>()) {
         gxy<C, false, S, S>(Xs, ar, Tm);  // + A T, one chain per row
       } else {
@@ -3471,15 +3502,20 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
       // and small_math.hpp cond_query do the same)
       const double ub = c < S - 1 ? NX[S - 1] : 0.0;
       const double sg = (bcast<S - 1>(NX[S - 1]) + 1.0) * (1.0 / KOFF);
-      bad = bad || !(sg > 0.0);
-      flag(!(sg > 0.0), 1, k + 1);
+      if constexpr (FOLD) {
+        pS = sg;  // a NaN sigma: the minimum drops it, the probe keeps it
+        fmin = __builtin_fmin(fmin, sg);
+      } else {
+        bad = bad || !(sg > 0.0);
+        flag(!(sg > 0.0), 1, k + 1);
+      }
       // P = diag(P11^-1 - KOFF I, 0) has a zero last row and column, so W^-T P W^-1 = P:
       // it is added before the congruence (no copy of Sigma's rows needed)
       double rq[S];
 #pragma unroll
       for (int i = 0; i < S - 1; ++i) {
         // one three-address v_fma_f64 (hipcc emitted a copy of X[i] + v_fmac: 12 moves)
-        if constexpr (kFma3)
+        if constexpr (LEAN1)
           asm("v_fma_f64 %0, %1, %2, %3" : "=v"(rq[i]) : "v"(kmask), "v"(NX[i]), "v"(X[i]));
         else
           rq[i] = __builtin_fma(kmask, NX[i], X[i]);
@@ -3489,11 +3525,13 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
       LaneB<S - 1>::fma(reinterpret_cast<double (&)[S - 1]>(rq), ub, rq[S - 1]);  // W^-T (.)
       rq[S - 1] = __builtin_fma(e_last, recip_nr(sg) - KOFF, rq[S - 1]);  // + 1/sigma - KOFF
       double acc = 0.0, dmin = 1.0;
-      ElimQ<S>::run(rq, acc, dmin, KOFF);
+      ElimQ<S>::run(rq, acc, FOLD ? fmin : dmin, KOFF);
       const double q = bcast<S>(acc);
       const double gam = bcast<S>(X[S]);
-      bad = bad || !(dmin > 0.0) || (q != q);
-      flag(!(dmin > 0.0) || (q != q), 16, k + 1);
+      if constexpr (!FOLD) {  // FOLD: a NaN q is a non-finite jk
+        bad = bad || !(dmin > 0.0) || (q != q);
+        flag(!(dmin > 0.0) || (q != q), 16, k + 1);
+      }
       jk = 0.5 * (q - gam);
     } else {
       double rq[S];
@@ -3510,8 +3548,15 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
     }
     stamp(7);
     if constexpr (TRAJ && !F32) tb.load_rows(cq, imT, c);
-    bad = bad || !finite_val(jk);
-    flag(!finite_val(jk), 32, k + 1);
+    if constexpr (FOLD) {
+      // the step's one test: any pivot or sigma <= 0, a NaN probe, a non-finite J
+      const bool f = !(fmin > 0.0) | __builtin_isunordered(pNE, pNX) |
+                     __builtin_isunordered(pU, pS) | !finite_val(jk);
+      bad = bad | f;
+    } else {
+      bad = bad || !finite_val(jk);
+      flag(!finite_val(jk), 32, k + 1);
+    }
     kf1 = (bad && kf1 == 0) ? k + 2 : kf1;  // first flagged horizon + 1
     if (fuse_argmin) {
       const int t = k + 1;
