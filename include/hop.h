@@ -110,6 +110,9 @@ const char* hop_last_error(void);
  *       clamped to HOP_HANDOVER_H_MAX (a clamped h only makes the triage decline)
  *   developer builds under HOP_OPT_NO_RERUN also put the reason of the first flag
  *   in bits HOP_HANDOVER_REASON_SHIFT .. HOP_HANDOVER_SHIFT - 1
+ * How the library tells the two launches their parts, and what HOP_OPT_FORCE_HANDOVER,
+ * HOP_OPT_NO_RERUN and HOP_OPT_REFERENCE_ASSOC change on each path, is internal:
+ * LftArgs::cond in time_opt_ilqr_amd/csrc/hop_kernels.hpp, the one definition.
  */
 #define HOP_HANDOVER_SHIFT 13
 #define HOP_HANDOVER_H_MAX 262143 /* 2^18 - 1: h << 13 stays below the int32 sign bit */

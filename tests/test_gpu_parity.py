@@ -537,6 +537,45 @@ def test_cond_fp32_blocks_config5_shape(dev, golden_dir):
     assert _elem_rel(gen.J.cpu().numpy(), d["J"]) <= 2e-3
 
 
+def test_cond_fp32_blocks_no_rerun_skips_the_second_launch(dev):
+    """fp32 blocks at s = 13, m = 4 under HOP_OPT_NO_RERUN: the conditioned kernel
+    alone, no second launch (no triage on this path), so a problem it hands over (Q_3 =
+    -I: chol_inv's LU slot in the reference, utils.py:69-93) keeps the hand-over word
+    and every other problem the conditioned kernel's J and status 0; with
+    HOP_OPT_FORCE_HANDOVER too, every problem keeps HOP_HANDOVER_WORD(0).  Without
+    NO_RERUN the handed-over problem is the generic fp32 kernel's, bitwise
+    (HOP_OPT_REFERENCE_ASSOC), as is the whole forced batch.  Five problems, six
+    steps: one full wave and a tail of one."""
+    import torch
+    from time_opt_ilqr_amd import _lib, engine
+    Bn, s, m, N, b, k = 5, 13, 4, 6, 2, 3
+    A, Bm, Q, R, Ri, z0, QT = orc.synth_lft_batch(4848, Bn, s, m, N)
+    Q = Q.copy()
+    Q[b, k] = -np.eye(s)
+    args = [_t(x, dev, torch.float32) for x in (A, Bm, Q, Ri, z0[0], QT)]
+    kw = dict(t_min=2, t_max=N)
+    d = engine.propagate(*args, **kw)
+    with _lib.options(reference_assoc=True):
+        r = engine.propagate(*args, **kw)
+    with _lib.options(no_rerun=True):
+        nr = engine.propagate(*args, **kw)
+    with _lib.options(no_rerun=True, force_handover=True):
+        nf = engine.propagate(*args, **kw)
+    with _lib.options(force_handover=True):
+        f = engine.propagate(*args, **kw)
+    torch.cuda.synchronize()
+    ok = [i for i in range(Bn) if i != b]
+    st = nr.status.cpu().numpy()
+    assert st[b] & _lib.ST_HANDOVER and (st[ok] == 0).all(), st
+    assert (nf.status.cpu().numpy() == _lib.ST_HANDOVER).all(), nf.status
+    assert int(r.status[b]) & orc.ST_LU
+    nn = lambda x: x.nan_to_num(7.0)  # noqa: E731  (NaN patterns compare equal)
+    assert torch.equal(d.status, r.status) and torch.equal(nn(d.J[b]), nn(r.J[b]))
+    assert torch.equal(d.J[ok], nr.J[ok])  # not handed over: the first launch's values
+    assert torch.equal(nn(f.J), nn(r.J)) and torch.equal(f.status, r.status)
+    assert torch.equal(f.t_star, r.t_star) and torch.equal(nn(f.j_star), nn(r.j_star))
+
+
 def test_cond_nonfinite_short_horizons_and_tails(dev):
     """Default s=13 path (conditioned kernel + rerun): a NaN block is handed over and
     reported exactly as the reference association reports it (non-finite J at that

@@ -87,6 +87,34 @@ struct AugArgs {
   T* z0;      // [s] or null: z0 = e_s (augmented.py:57)
 };
 
+// The hand-over protocol (LftArgs::cond).  Every fast LFT path is two launches: a
+// conditioned-prefix kernel takes all problems and leaves the hand-over word
+// (include/hop.h) in the status of those it cannot take; a rerun launch recomputes
+// exactly those with the reference association.  The host tells each launch its part
+// through LftArgs::cond (cond_first_word / cond_rerun_word below):
+//   first launch  0: every problem computed.  HOP_OPT_FORCE_HANDOVER: kCondFlagAll.
+//                 Developer builds under HOP_OPT_NO_RERUN: kCondReason too, where the
+//                 path carries the reason field.
+//   rerun launch  kCondRerun: only the problems whose status carries ST_RERUN.  The
+//                 s = 13 fp64 kernels first triage them (a hand-over explained by
+//                 non-finite inputs takes the reference's outcome, no recompute), but
+//                 not under HOP_OPT_FORCE_HANDOVER (kCondForced).  HOP_OPT_NO_RERUN: the
+//                 launch is skipped and the hand-over words stay in status; the paths
+//                 that triage launch it with kCondTriageOnly, for the triage alone.
+//   HOP_OPT_REFERENCE_ASSOC: no pair; the reference kernel alone, cond as the caller
+//                 gave it (0: every problem).
+// Which of this a path does is its CondPolicy (below).  Bits: who sets -> who reads.
+constexpr int kCondRerun = 1;        // rerun word; the fused bodies (device) -> LFT kernels
+constexpr int kCondFlagAll = 2;      // first word, FORCE_HANDOVER -> conditioned kernels
+constexpr int kCondReason = 4;       // dev builds, NO_RERUN -> lft_sweep_v2.hip's cond kernels
+constexpr int kCondTriageOnly = 8;   // rerun word, NO_RERUN -> s = 13 fp64 rerun kernels
+constexpr int kCondForced = 16;      // rerun word, FORCE_HANDOVER -> s = 13 fp64 rerun kernels
+constexpr int kCondRerunOnly = 64;   // row-group rerun word -> dispatch_lft_small (host)
+static_assert((kCondRerun | kCondFlagAll | kCondReason | kCondTriageOnly | kCondForced |
+               kCondRerunOnly) == kCondRerun + kCondFlagAll + kCondReason + kCondTriageOnly +
+                                      kCondForced + kCondRerunOnly,
+              "the cond bits are pairwise disjoint");
+
 template <class T>
 struct LftArgs {
   const T* A;    // [B][nalloc][s][s]   augmented A_k
@@ -106,8 +134,7 @@ struct LftArgs {
   T* dbg_efg;        // [B][n][3][s][s] or null  (E_k, F_k, G_k)
   T* dbg_pre;        // [B][n][3][s][s] or null  (Ebar_k, Fbar_k, Gbar_k)
   int traj;          // 1: A/B/Q/QT unused, blocks built in-kernel from `tr`
-  int cond;          // SchedCond: bit 0 rerun launch (only ST_RERUN problems), bit 1 flag all;
-                     // kCondRerunOnly: dispatch_lft_small launches only its LFT rerun
+  int cond;          // the hand-over protocol's word: kCond* bits, described below this struct
   int tile64;        // 1: A/B/Q/QT in the tile64 layout [B/64][nalloc][block elems][64]
   TrajArgs<T> tr;
 };
@@ -250,9 +277,51 @@ hipError_t dispatch_dynamics(const DynArgs& a, hipStream_t stream);
 template <class T>
 hipError_t dispatch_lft(const LftArgs<T>& a, hipStream_t stream);
 hipError_t dispatch_lft_v2(const LftArgs<double>& a, hipStream_t stream);
-// the small-s row-group kernel's hand-overs go to lft_small.hip's LFT instantiation
-// (its rerun launch alone): LftArgs.cond = 1 | kCondRerunOnly
-constexpr int kCondRerunOnly = 64;
+// What a path does with the protocol:
+//   kCondPolicyS13 (s = 13 fp64, augmented and trajectory form: default, packed, the
+//     developer schedules with a rerun): the first word carries the reason bit in
+//     developer builds under NO_RERUN; under NO_RERUN the second launch still runs,
+//     for the triage alone, with the reason bit; it is told of a forced hand-over.
+//   kCondPolicyRowGroup (small-s row groups, lft_sweep_v2.hip): first word as above;
+//     under NO_RERUN no second launch; the rerun goes through dispatch_lft_small with
+//     kCondRerunOnly and is not told of a forced hand-over (no triage there).
+//   kCondPolicyPlain (lft_small.hip, every shape, layout and dtype; fp32 s = 13, whose
+//     rerun goes through dispatch_lft<float>): first word 0 or kCondFlagAll; under
+//     NO_RERUN no second launch; rerun word kCondRerun.
+//   kCondPolicyFused (developer variants 60, 61): first word 0 or kCondFlagAll; no
+//     second launch from the host (the kernel recomputes its own hand-overs).
+// A developer variant that times the first kernel alone clears `rerun` in its copy.
+struct CondPolicy {
+  bool reason;  // developer builds under NO_RERUN: the words carry kCondReason
+  bool triage;  // under NO_RERUN the second launch still runs, with kCondTriageOnly
+  bool forced;  // the rerun word carries kCondForced under FORCE_HANDOVER
+  bool rerun;   // a second launch follows the first
+  int extra;    // or'ed into the rerun word (kCondRerunOnly)
+};
+constexpr CondPolicy kCondPolicyS13 = {true, true, true, true, 0};
+constexpr CondPolicy kCondPolicyRowGroup = {true, false, false, true, kCondRerunOnly};
+constexpr CondPolicy kCondPolicyPlain = {false, false, false, true, 0};
+constexpr CondPolicy kCondPolicyFused = {false, false, false, false, 0};
+inline int cond_first_word(const CondPolicy& p) {
+  return (opt(HOP_OPT_FORCE_HANDOVER) ? kCondFlagAll : 0) |
+         ((p.reason && kDevBuild && opt(HOP_OPT_NO_RERUN)) ? kCondReason : 0);
+}
+inline int cond_rerun_word(const CondPolicy& p) {
+  return kCondRerun | p.extra | ((p.forced && opt(HOP_OPT_FORCE_HANDOVER)) ? kCondForced : 0) |
+         (opt(HOP_OPT_NO_RERUN) ? kCondTriageOnly | (cond_first_word(p) & kCondReason) : 0);
+}
+template <class T>
+LftArgs<T> with_cond(LftArgs<T> a, int cond) { a.cond = cond; return a; }
+// The launch pair: first(args with the first word), then rerun(args with the rerun
+// word) unless the first failed or the policy has no second launch.  Either callable
+// returns its hipError_t; rerun may be another dispatcher.
+template <class T, class First, class Rerun>
+hipError_t launch_cond_pair(const LftArgs<T>& a, const CondPolicy& p, First&& first,
+                            Rerun&& rerun) {
+  const hipError_t e = first(with_cond(a, cond_first_word(p)));
+  if (e != hipSuccess || !p.rerun || (opt(HOP_OPT_NO_RERUN) && !p.triage)) return e;
+  return rerun(with_cond(a, cond_rerun_word(p)));
+}
 // fp64 s <= 5 augmented blocks on the conditioned kernel's row groups (lft_sweep_v2.hip)
 // for batches up to kSmallRowGroupMax (above it lft_small.hip's one problem per lane
 // fills the chip and wins: profiles/r06_small_rg_crossover.jsonl); HOP_OPT_SMALL_LANE

@@ -180,7 +180,7 @@ __device__ __forceinline__ void read_block(const unsigned char* wimg, int slot, 
 
 // COND: the conditioned-prefix association (small_math.hpp cond_*; DESIGN.md
 // 3.0) with first-attempt inverses; problems it cannot take get status 16 and
-// are recomputed by the LFT instantiation in rerun mode (a.cond & 1).
+// are recomputed by the LFT instantiation in rerun mode (a.cond & kCondRerun).
 // EXP (developer builds, timing experiments only -- results are wrong): 1 drops
 // the arithmetic (the LDS images are only summed), 2 streams step 0 only
 // PM: problem-major pieces (the wave's 64 CM chunks of a block in problem order,
@@ -202,7 +202,7 @@ __device__ __forceinline__ void lft_small_body(const LftArgs<T>& a) {
   const long long pb = prob < a.batch ? prob : a.batch - 1;
   if (wave_prob0 >= a.batch) return;  // wave-uniform; no workgroup barrier in this kernel
   const long long pb0 = wave_prob0;
-  if (!COND && (a.cond & 1)) {  // rerun launch: only the problems the COND kernel handed over
+  if (!COND && (a.cond & kCondRerun)) {  // only the problems the COND kernel handed over
     const bool need = valid && (a.status[prob] & 16);
     if (!__any(need)) return;  // wave-uniform; no workgroup barrier in this kernel
     valid = need;
@@ -275,7 +275,7 @@ __device__ __forceinline__ void lft_small_body(const LftArgs<T>& a) {
   CondState<T, S, MM> cs;
   if constexpr (COND) {
     cond_init(cs, z);
-    cs.bad = (a.cond & 2) != 0;
+    cs.bad = (a.cond & kCondFlagAll) != 0;
     cs.kf1 = cs.bad ? 1 : 0;
   }
   T rinv[MM][MM];
@@ -651,7 +651,7 @@ __device__ __forceinline__ void pipe_small_problem(const LftArgs<T>& a, long lon
   __syncthreads();  // the next problem reuses the rings and the status word
 }
 
-// The rerun launch after the conditioned small-s kernels (a.cond bit 0): the
+// The rerun launch after the conditioned small-s kernels (kCondRerun): the
 // workgroup's hand-overs (status 16) by the pipeline when there are at most
 // kSmallPipeMax of them, else by the one-lane body
 template <class T, int S, int MM>
@@ -661,7 +661,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void l
   static_assert(G::WPB >= 3, "the pipeline needs three waves per workgroup");
   static_assert(PG::BYTES <= G::WAVE_BYTES * G::WPB, "the rings must fit the LFT kernel's LDS");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  if (!(a.cond & 1)) {  // not a rerun (HOP_OPT_REFERENCE_ASSOC): every problem, one per lane
+  if (!(a.cond & kCondRerun)) {  // HOP_OPT_REFERENCE_ASSOC: every problem, one per lane
     lft_small_body<T, S, MM, false, 64, 0, 1>(a);
     return;
   }
@@ -743,7 +743,7 @@ __global__ __launch_bounds__(256, 1) void lft_small_traj_kernel(LftArgs<T> a) {
   const long long pb = valid ? prob : a.batch - 1;
   if (wave_prob0 >= a.batch) return;  // wave-uniform; no workgroup barrier in this kernel
   const long long pb0 = wave_prob0;
-  if (!COND && (a.cond & 1)) {  // rerun launch (see lft_small_kernel)
+  if (!COND && (a.cond & kCondRerun)) {  // rerun launch (see lft_small_kernel)
     const bool need = valid && (a.status[prob] & 16);
     if (!__any(need)) return;
     valid = need;
@@ -874,7 +874,7 @@ __global__ __launch_bounds__(256, 1) void lft_small_traj_kernel(LftArgs<T> a) {
   CondState<T, S, MM> cs;
   if constexpr (COND) {
     cond_init(cs, z);
-    cs.bad = (a.cond & 2) != 0;
+    cs.bad = (a.cond & kCondFlagAll) != 0;
     cs.kf1 = cs.bad ? 1 : 0;
   }
   T rinv[MM][MM];  // R_inv_cached
@@ -1020,92 +1020,6 @@ hipError_t dispatch_lft_small(const LftArgs<T>& a, hipStream_t stream) {
   // Batch-major blocks stream as problem-major pieces (LY 1); tile64 blocks (LY 2)
   // as contiguous 1-KiB pieces.  The batch-major stream is the bound at config 3:
   // its DMA alone takes 1.54 ms, the tile64 one 0.80 ms (tools/exp_tiled.py).
-  // Developer builds also carry the conditioned-prefix instantiation (variant 61:
-  // it, then the LFT instantiation in rerun mode for the problems it flagged; 62:
-  // the COND kernel alone, A/B) and the layout / occupancy experiments (72-78).
-  // The conditioned step issues half the FLOPs but its loop-carried chain is no
-  // shorter, and the stream, not the arithmetic, bounds this kernel
-  using small::LaunchGeo;
-  auto launch = [&](auto kern, LaunchGeo g, const LftArgs<T>& args) {
-    const long long blocks = (a.batch + g.ppb - 1) / g.ppb;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3((unsigned)g.tpb), (size_t)g.bytes, stream,
-                       args);
-    return hipGetLastError();
-  };
-  auto go1 = [&](auto kl, LaunchGeo g) { return launch(kl, g, a); };
-#ifdef HOP_DEV
-  // cmode 1: the product default (conditioned + rerun), 2: COND alone (62),
-  // 0: the LFT association alone (HOP_OPT_REFERENCE_ASSOC)
-  const int cmode = opt(HOP_OPT_REFERENCE_ASSOC) ? 0 : g_opt_variant == 62 ? 2 : 1;
-  auto go2 = [&](auto kc, auto kl, LaunchGeo g) {
-    if (cmode == 0 || (a.cond & kCondRerunOnly)) return go1(kl, g);
-    LftArgs<T> c = a;
-    c.cond = opt(HOP_OPT_FORCE_HANDOVER) ? 2 : 0;  // 2: hand every problem over (tests)
-    const hipError_t e = launch(kc, g, c);
-    if (e != hipSuccess || cmode == 2 || opt(HOP_OPT_NO_RERUN)) return e;
-    LftArgs<T> r = a;
-    r.cond = 1;
-    return launch(kl, g, r);
-  };
-  // the trajectory form (both layouts): the conditioned association + the LFT rerun
-  // (the product default); variant 79: the LFT association alone, 62: COND alone
-  auto go2t = [&](auto kc, auto kl, LaunchGeo g) {
-    if (g_opt_variant == 79 || opt(HOP_OPT_REFERENCE_ASSOC)) return go1(kl, g);
-    LftArgs<T> c = a;
-    c.cond = opt(HOP_OPT_FORCE_HANDOVER) ? 2 : 0;
-    const hipError_t e = launch(kc, g, c);
-    if (e != hipSuccess || g_opt_variant == 62 || opt(HOP_OPT_NO_RERUN)) return e;
-    LftArgs<T> r = a;
-    r.cond = 1;
-    return launch(kl, g, r);
-  };
-#define HOP_SMALL_TRAJ(S_, M_)                                                            \
-  if (a.traj && a.s == S_ && a.m == M_)                                                   \
-    return a.tile64 ? go2t(small::lft_small_traj_kernel<T, S_, M_, true, 2>,              \
-                           small::lft_small_traj_kernel<T, S_, M_, false, 2>,             \
-                           small::geo_of<small::GeoT<T, S_, M_>>())                       \
-                    : go2t(small::lft_small_traj_kernel<T, S_, M_, true, 0>,              \
-                           small::lft_small_traj_kernel<T, S_, M_, false, 0>,             \
-                           small::geo_of<small::GeoT<T, S_, M_>>());
-#define HOP_SMALL_TRAJ_DEV(S_, M_) HOP_SMALL_TRAJ(S_, M_)
-  // variant 72: 32 problems per wave (two waves per SIMD), A/B against 64;
-  // 73: the conditioned association at 32 problems per wave + the rerun launch
-#define HOP_SMALL(S_, M_)                                                                 \
-  if (a.s == S_ && a.m == M_) {                                                           \
-    HOP_SMALL_TRAJ_DEV(S_, M_)                                                            \
-    if (a.tile64) {                                                                       \
-      if (cmode != 0)                                                                     \
-        return go2(small::lft_small_kernel<T, S_, M_, true, 64, 0, 2>,                    \
-                   small::lft_small_kernel<T, S_, M_, false, 64, 0, 2>,                   \
-                   small::geo_of<small::Geo<T, S_, M_>>());                                \
-      if (g_opt_variant == 78)                                                            \
-        return go1(small::lft_small_kernel<T, S_, M_, false, 64, 1, 2>,                   \
-                   small::geo_of<small::Geo<T, S_, M_>>());                                \
-      return go1(small::lft_small_kernel<T, S_, M_, false, 64, 0, 2>,                     \
-                 small::geo_of<small::Geo<T, S_, M_>>());                                  \
-    }                                                                                     \
-    if (!a.traj && g_opt_variant == 72)                                                   \
-      return go1(small::lft_small_kernel<T, S_, M_, false, 32>,                           \
-                 small::geo_of<small::Geo<T, S_, M_, 32>>()); \
-    if (!a.traj && (g_opt_variant == 74 || g_opt_variant == 75))                          \
-      return go1(g_opt_variant == 74 ? small::lft_small_kernel<T, S_, M_, false, 64, 1>     \
-                                     : small::lft_small_kernel<T, S_, M_, false, 64, 2>,    \
-                 small::geo_of<small::Geo<T, S_, M_>>());                                  \
-    if (!a.traj && g_opt_variant == 76)                                                   \
-      return go1(small::lft_small_kernel<T, S_, M_, false, 64, 0, 0>,                     \
-                 small::geo_of<small::Geo<T, S_, M_>>());                                  \
-    if (!a.traj && g_opt_variant == 77)                                                   \
-      return go1(small::lft_small_kernel<T, S_, M_, false, 64, 1, 1>,                     \
-                 small::geo_of<small::Geo<T, S_, M_>>());                                  \
-    if (!a.traj && g_opt_variant == 73)                                                   \
-      return go2(small::lft_small_kernel<T, S_, M_, true, 32>,                            \
-                 small::lft_small_kernel<T, S_, M_, false, 32>,                           \
-                 small::geo_of<small::Geo<T, S_, M_, 32>>()); \
-    return go2(small::lft_small_kernel<T, S_, M_, true, 64, 0, 1>,                        \
-               small::rerun_kernel<T, S_, M_>(),                                          \
-               small::geo_of<small::Geo<T, S_, M_>>());                                   \
-  }
-#else
   // Every small-s shape, both layouts and both dtypes: the conditioned association
   // (half the FLOPs; at config 3 its stream, not its arithmetic, is the bound:
   // 0.83 ms against 0.91 for the LFT and 0.81 for the stream alone), then the LFT
@@ -1114,46 +1028,85 @@ hipError_t dispatch_lft_small(const LftArgs<T>& a, hipStream_t stream) {
   // 1e-12 the conditioned form holds the 50-digit reference curve where the fp64
   // reference association is 1e-2 .. 1 off, so augmented blocks and
   // the trajectory form run the same arithmetic.  HOP_OPT_REFERENCE_ASSOC: the LFT
-  // kernel alone (the reference association; comparator for the tests and tools)
-  auto gocond = [&](auto kc, auto kl, LaunchGeo g) {
-    // the rerun launch alone: the hand-overs of lft_sweep_v2.hip's small-s row-group
-    // kernel (a.cond = 1 | kCondRerunOnly)
-    if (opt(HOP_OPT_REFERENCE_ASSOC) || (a.cond & kCondRerunOnly)) return go1(kl, g);
-    LftArgs<T> c = a;
-    c.cond = opt(HOP_OPT_FORCE_HANDOVER) ? 2 : 0;  // 2: hand every problem over (tests)
-    const hipError_t e = launch(kc, g, c);
-    if (e != hipSuccess || opt(HOP_OPT_NO_RERUN)) return e;  // hand-over words left in status
-    LftArgs<T> r = a;
-    r.cond = 1;
-    return launch(kl, g, r);
+  // kernel alone (the reference association; comparator for the tests and tools).
+  // Developer builds: variant 62 the COND kernel alone (A/B), 79 the trajectory form's
+  // LFT association alone, and the layout / occupancy experiments (72-78).
+  // The conditioned step's loop-carried chain is no shorter than the LFT's
+  using small::LaunchGeo;
+  auto launch = [&](auto kern, LaunchGeo g, const LftArgs<T>& args) {
+    const long long blocks = (a.batch + g.ppb - 1) / g.ppb;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3((unsigned)g.tpb), (size_t)g.bytes, stream,
+                       args);
+    return hipGetLastError();
+  };
+  auto go1 = [&](auto kl, LaunchGeo g) { return launch(kl, g, a); };
+  const int variant = kDevBuild ? g_opt_variant : 0;
+  const bool ref = opt(HOP_OPT_REFERENCE_ASSOC);
+  const bool ref_traj = ref || variant == 79;  // 79: the trajectory form's LFT association
+  const bool exp78 = ref && variant == 78;     // 78: a tile64 layout experiment (LFT kernel)
+  // the launch pair (kCondPolicyPlain, hop_kernels.hpp).  lft_only: the LFT kernel
+  // alone with the caller's word, which is also how the hand-overs of lft_sweep_v2.hip's
+  // small-s row-group kernel arrive (kCondRerunOnly: this dispatcher's rerun launch alone)
+  auto gopair = [&](auto kc, auto kl, LaunchGeo g, bool lft_only) {
+    if (lft_only || (a.cond & kCondRerunOnly)) return go1(kl, g);
+    CondPolicy p = kCondPolicyPlain;
+    p.rerun = variant != 62;
+    return launch_cond_pair(
+        a, p, [&](const LftArgs<T>& c) { return launch(kc, g, c); },
+        [&](const LftArgs<T>& r) { return launch(kl, g, r); });
   };
 #define HOP_SMALL_TRAJ(S_, M_)                                                            \
   if (a.traj && a.s == S_ && a.m == M_)                                                   \
-    return a.tile64 ? gocond(small::lft_small_traj_kernel<T, S_, M_, true, 2>,            \
+    return a.tile64 ? gopair(small::lft_small_traj_kernel<T, S_, M_, true, 2>,            \
                              small::lft_small_traj_kernel<T, S_, M_, false, 2>,           \
-                             small::geo_of<small::GeoT<T, S_, M_>>())                     \
-                    : gocond(small::lft_small_traj_kernel<T, S_, M_, true, 0>,            \
+                             small::geo_of<small::GeoT<T, S_, M_>>(), ref_traj)           \
+                    : gopair(small::lft_small_traj_kernel<T, S_, M_, true, 0>,            \
                              small::lft_small_traj_kernel<T, S_, M_, false, 0>,           \
-                             small::geo_of<small::GeoT<T, S_, M_>>());
+                             small::geo_of<small::GeoT<T, S_, M_>>(), ref_traj);
+#ifdef HOP_DEV
+  // variant 78 (tile64, reference association), 74-77 (batch-major): layout experiments
+  // of the LFT kernel; 72: 32 problems per wave (two waves per SIMD), A/B against 64;
+  // 73: the conditioned association at 32 problems per wave + the rerun launch
+#define HOP_SMALL_DEV(S_, M_)                                                             \
+  if (a.tile64) /* only exp78 comes here with tile64 blocks */                            \
+    return go1(small::lft_small_kernel<T, S_, M_, false, 64, 1, 2>,                       \
+               small::geo_of<small::Geo<T, S_, M_>>());                                   \
+  if (variant == 72)                                                                      \
+    return go1(small::lft_small_kernel<T, S_, M_, false, 32>,                             \
+               small::geo_of<small::Geo<T, S_, M_, 32>>());                               \
+  if (variant == 74 || variant == 75)                                                     \
+    return go1(variant == 74 ? small::lft_small_kernel<T, S_, M_, false, 64, 1>           \
+                             : small::lft_small_kernel<T, S_, M_, false, 64, 2>,          \
+               small::geo_of<small::Geo<T, S_, M_>>());                                   \
+  if (variant == 76)                                                                      \
+    return go1(small::lft_small_kernel<T, S_, M_, false, 64, 0, 0>,                       \
+               small::geo_of<small::Geo<T, S_, M_>>());                                   \
+  if (variant == 77)                                                                      \
+    return go1(small::lft_small_kernel<T, S_, M_, false, 64, 1, 1>,                       \
+               small::geo_of<small::Geo<T, S_, M_>>());                                   \
+  if (variant == 73)                                                                      \
+    return gopair(small::lft_small_kernel<T, S_, M_, true, 32>,                           \
+                  small::lft_small_kernel<T, S_, M_, false, 32>,                          \
+                  small::geo_of<small::Geo<T, S_, M_, 32>>(), ref);
+#else
+#define HOP_SMALL_DEV(S_, M_)
+#endif
 #define HOP_SMALL(S_, M_)                                                                 \
   HOP_SMALL_TRAJ(S_, M_)                                                                  \
   if (a.s == S_ && a.m == M_) {                                                           \
-    return a.tile64 ? gocond(small::lft_small_kernel<T, S_, M_, true, 64, 0, 2>,          \
-                             small::lft_small_kernel<T, S_, M_, false, 64, 0, 2>,         \
-                             small::geo_of<small::Geo<T, S_, M_>>())                      \
-                    : gocond(small::lft_small_kernel<T, S_, M_, true, 64, 0, 1>,          \
-                             small::rerun_kernel<T, S_, M_>(),                            \
-                             small::geo_of<small::Geo<T, S_, M_>>());                     \
+    if (a.tile64 && !exp78)                                                               \
+      return gopair(small::lft_small_kernel<T, S_, M_, true, 64, 0, 2>,                   \
+                    small::lft_small_kernel<T, S_, M_, false, 64, 0, 2>,                  \
+                    small::geo_of<small::Geo<T, S_, M_>>(), ref);                         \
+    HOP_SMALL_DEV(S_, M_)                                                                 \
+    return gopair(small::lft_small_kernel<T, S_, M_, true, 64, 0, 1>,                     \
+                  small::rerun_kernel<T, S_, M_>(),                                       \
+                  small::geo_of<small::Geo<T, S_, M_>>(), ref);                           \
   }
-#endif
-  if constexpr (sizeof(T) == 4) {
-    HOP_SMALL(2, 1) HOP_SMALL(3, 1) HOP_SMALL(4, 1) HOP_SMALL(4, 2) HOP_SMALL(5, 1)
-    HOP_SMALL(5, 2)  // s = 6 spills: generic kernel
-  } else {
-    HOP_SMALL(2, 1) HOP_SMALL(3, 1) HOP_SMALL(4, 1) HOP_SMALL(4, 2) HOP_SMALL(5, 1)
-    HOP_SMALL(5, 2)
-  }
+  HOP_SMALL(2, 1) HOP_SMALL(3, 1) HOP_SMALL(4, 1) HOP_SMALL(4, 2) HOP_SMALL(5, 1)
+  HOP_SMALL(5, 2)  // fp32 s = 6 spills: generic kernel
 #undef HOP_SMALL
+#undef HOP_SMALL_DEV
 #undef HOP_SMALL_TRAJ
   return hipErrorNotSupported;
 }

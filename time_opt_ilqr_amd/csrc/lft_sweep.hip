@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256, 1) void lft_sweep_kernel(LftArgs<T> a) {
   const long long prob = ((long long)blockIdx.x * kWavesPerBlock + w) * kProbPerWave + g;
   bool valid = prob < a.batch;
   const long long pb = valid ? prob : a.batch - 1;
-  if (a.cond & 1) {  // rerun launch after the conditioned-prefix kernel (fp32 blocks)
+  if (a.cond & kCondRerun) {  // after the conditioned-prefix kernel (fp32 blocks)
     const bool need = valid && (a.status[prob] & (int)ST_RERUN);
     if (!__any(need)) return;  // wave-uniform; no workgroup barrier in this kernel
     valid = need;

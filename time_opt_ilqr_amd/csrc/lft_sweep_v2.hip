@@ -1454,16 +1454,16 @@ __device__ __forceinline__ void lft_v2_body(LftArgs<double> a, int need_in) {
   if (need_in >= 0) {  // fused hand-over: the caller's flags
     valid = valid && need_in != 0;
     if (!__any(valid)) return;
-  } else if (a.cond & 1) {  // rerun launch after SchedCond: only the problems it handed over
+  } else if (a.cond & kCondRerun) {  // after SchedCond: only the problems it handed over
     const int st_in = valid ? a.status[prob] : 0;
     bool need = valid && (st_in & (int)ST_RERUN);
     // hand-overs explained by non-finite inputs take the reference's outcome here
-    // instead of a recompute (bit 4: a forced hand-over, never triaged)
-    if (!(a.cond & 16) && __any(need)) {  // called by the whole wave (lane-0 writes, shuffles)
+    // instead of a recompute (a forced hand-over is never triaged)
+    if (!(a.cond & kCondForced) && __any(need)) {  // the whole wave (lane-0 writes, shuffles)
       const bool resolved = nonfinite_resolve<S, MM, TRAJ>(a, lane, g, wave_prob0, need, st_in);
       need = need && !resolved;
     }
-    if (a.cond & 8) return;  // triage only (HOP_OPT_NO_RERUN): the rest keep their hand-over word
+    if (a.cond & kCondTriageOnly) return;  // the rest keep their hand-over word
     if (!__any(need)) return;  // wave-uniform; no workgroup barrier in this kernel
     valid = need;
   }
@@ -2524,8 +2524,7 @@ __device__ __forceinline__ void pipe_problem(const LftArgs<double>& a, long long
 // The rerun launch after the s = 13 conditioned kernel (augmented blocks): the
 // non-finite triage of every handed-over problem (as lft_v2_body's rerun mode), then
 // the pipelined recompute of what is left (kPipeMax problems or fewer per workgroup)
-// or, above that, the LFT body on every wave (a.cond as in lft_v2_body: bit 0 rerun,
-// 4 developer reason bits, 8 triage only, 16 forced hand-over: no triage).
+// or, above that, the LFT body on every wave (a.cond: the rerun word, hop_kernels.hpp).
 template <class C, int S, int MM, int BS>
 __global__ __launch_bounds__(256, 1) void lft_rerun_pipe_kernel(LftArgs<double> a) {
   using PG = PipeGeo<S, MM, BS>;
@@ -2537,7 +2536,7 @@ __global__ __launch_bounds__(256, 1) void lft_rerun_pipe_kernel(LftArgs<double> 
   const bool valid = prob < a.batch;
   const int st_in = valid ? a.status[prob] : 0;
   bool need = valid && (st_in & (int)ST_RERUN);
-  if (!(a.cond & 16) && __any(need)) {  // the whole wave (lane-0 writes, shuffles)
+  if (!(a.cond & kCondForced) && __any(need)) {  // the whole wave (lane-0 writes, shuffles)
     const bool resolved =
         nonfinite_resolve<S, MM, has_traj<C>()>(a, lane, g, wave_prob0, need, st_in);
     need = need && !resolved;
@@ -2545,7 +2544,7 @@ __global__ __launch_bounds__(256, 1) void lft_rerun_pipe_kernel(LftArgs<double> 
   int* flags = reinterpret_cast<int*>(smem_raw + PG::OFF_MISC);
   if (c == 0) flags[w * 4 + g] = need ? 1 : 0;
   __syncthreads();
-  if (a.cond & 8) return;  // triage only (HOP_OPT_NO_RERUN): the rest keep their hand-over word
+  if (a.cond & kCondTriageOnly) return;  // the rest keep their hand-over word
   int cnt = 0;
 #pragma unroll
   for (int i = 0; i < kProbPerBlock; ++i) cnt += flags[i];
@@ -2940,7 +2939,7 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
   });
   X[S] = 0.0;
   const double e_s = (c == S) ? 1.0 : 0.0;  // row S of A~^T: carries m through the first product
-  bool bad = (a.cond & 2) != 0;
+  bool bad = (a.cond & kCondFlagAll) != 0;
   // the first flagged horizon + 1 (0: none; 1: the prologue or a forced hand-over),
   // left in status bits 13.. for the rerun launch's non-finite triage
   int kf1 = bad ? 1 : 0;
@@ -3590,9 +3589,10 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
   }
   if (valid && c == 0) {
     if (!QPIPE && N > 0) a.J[prob * N + N - 1] = (T)jprev;
-    // the hand-over word (include/hop.h); the developer reason field under cond & 4
-    a.status[prob] = bad ? ((a.cond & 4) ? (int)ST_RERUN | why << HOP_HANDOVER_REASON_SHIFT
-                                         : HOP_HANDOVER_WORD(kf1 - 1))
+    // the hand-over word (include/hop.h); the developer reason field under kCondReason
+    a.status[prob] = bad ? ((a.cond & kCondReason)
+                                ? (int)ST_RERUN | why << HOP_HANDOVER_REASON_SHIFT
+                                : HOP_HANDOVER_WORD(kf1 - 1))
                          : 0;
     if (fuse_argmin && a.t_star != nullptr) {
       a.t_star[prob] = tbest;
@@ -3604,7 +3604,7 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
     const bool hand = valid && bad;
     if (__any(hand)) {  // wave-uniform; the rerun body uses this wave's LDS only
       LftArgs<double> r = a;
-      r.cond = 1;
+      r.cond = kCondRerun;
       using RC = std::conditional_t<TRAJ, SchedLdlTraj, SchedLdlDma>;
       lft_v2_body<RC, S, MM>(r, hand ? 1 : 0);
     }
@@ -3697,12 +3697,12 @@ __global__ __launch_bounds__(256, 1) void lft_cond_cf_kernel(LftArgs<double> a) 
   const bool in = c < NN;
   const int cc = in ? c : 0;
   const double eps = 1e-9;
-  bool bad = (a.cond & 2) != 0;
+  bool bad = (a.cond & kCondFlagAll) != 0;
   // the first flagged horizon + 1 (0: none; 1: the prologue or a forced hand-over),
   // left in status bits 13.. for the rerun launch's non-finite triage
   int kf1 = bad ? 1 : 0;
   // developer builds: the first failing test and its horizon (hand-over diagnosis,
-  // reported in status bits 5.. under a.cond & 4); product builds compile none of it
+  // reported in status bits 5.. under kCondReason); product builds compile none of it
   int why = 0;
   auto flag = [&](bool f, int bit, int t) {
     if constexpr (kDevBuild) why = (f && why == 0) ? (bit | (t << 8)) : why;
@@ -3968,8 +3968,9 @@ __global__ __launch_bounds__(256, 1) void lft_cond_cf_kernel(LftArgs<double> a) 
   dma_wait();
   if (valid && c == 0) {
     if (N > 0) a.J[prob * N + N - 1] = jprev;
-    a.status[prob] = bad ? ((a.cond & 4) ? (int)ST_RERUN | why << HOP_HANDOVER_REASON_SHIFT
-                                         : HOP_HANDOVER_WORD(kf1 - 1))
+    a.status[prob] = bad ? ((a.cond & kCondReason)
+                                ? (int)ST_RERUN | why << HOP_HANDOVER_REASON_SHIFT
+                                : HOP_HANDOVER_WORD(kf1 - 1))
                          : 0;
     if (fuse_argmin && a.t_star != nullptr) {
       a.t_star[prob] = tbest;
@@ -3980,7 +3981,7 @@ __global__ __launch_bounds__(256, 1) void lft_cond_cf_kernel(LftArgs<double> a) 
     const bool hand = valid && bad;
     if (__any(hand)) {
       LftArgs<double> r = a;
-      r.cond = 1;
+      r.cond = kCondRerun;
       lft_v2_body<SchedLdlTraj, S, MM>(r, hand ? 1 : 0);
     }
   }
@@ -3992,9 +3993,9 @@ __global__ __launch_bounds__(256, 1) void lft_cond_cf_kernel(LftArgs<double> a) 
 // when the batch leaves lft_small.hip's one-problem-per-lane kernel most SIMDs idle
 // (B / 64 waves).  Four problems per wave (one per DPP row),
 // so B = 4,096 runs 1,024 waves.  Its hand-overs go to lft_small.hip's LFT
-// instantiation (the rerun launch alone: cond = 1 | kCondRerunOnly), whose chol_inv
-// ladders and status bits are the reference's.  Larger batches (and tile64 blocks, the
-// trajectory form, per-step R, debug outputs) stay on lft_small.hip.
+// instantiation (the rerun launch alone: kCondPolicyRowGroup, hop_kernels.hpp), whose
+// chol_inv ladders and status bits are the reference's.  Larger batches (and tile64
+// blocks, the trajectory form, per-step R, debug outputs) stay on lft_small.hip.
 // The crossover batch (kSmallRowGroupMax, hop_kernels.hpp): tools/bench_small_rg.py.
 namespace v2 {
 template <int S, int MM>
@@ -4002,16 +4003,14 @@ hipError_t launch_cond_small(const LftArgs<double>& a, hipStream_t stream) {
   using G = Geo<S, MM, 8, false, true>;
   static_assert(G::WAVE_BYTES * kWavesPerBlock <= 64 * 1024, "several workgroups per CU");
   const long long blocks = (a.batch + kProbPerBlock - 1) / kProbPerBlock;
-  const bool force = opt(HOP_OPT_FORCE_HANDOVER);
-  LftArgs<double> c = a;
-  c.cond = (force ? 2 : 0) | ((kDevBuild && opt(HOP_OPT_NO_RERUN)) ? 4 : 0);
-  hipLaunchKernelGGL((lft_cond_kernel<SchedCondSmall, S, MM>), dim3((unsigned)blocks), dim3(256),
-                     (size_t)(G::WAVE_BYTES * kWavesPerBlock), stream, c);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess || opt(HOP_OPT_NO_RERUN)) return e;  // hand-over words left in status
-  LftArgs<double> r = a;
-  r.cond = 1 | kCondRerunOnly;
-  return dispatch_lft_small<double>(r, stream);
+  return launch_cond_pair(
+      a, kCondPolicyRowGroup,
+      [&](const LftArgs<double>& c) {
+        hipLaunchKernelGGL((lft_cond_kernel<SchedCondSmall, S, MM>), dim3((unsigned)blocks),
+                           dim3(256), (size_t)(G::WAVE_BYTES * kWavesPerBlock), stream, c);
+        return hipGetLastError();
+      },
+      [&](const LftArgs<double>& r) { return dispatch_lft_small<double>(r, stream); });
 }
 }  // namespace v2
 hipError_t dispatch_cond_small(const LftArgs<double>& a, hipStream_t stream) {
@@ -4042,21 +4041,17 @@ hipError_t dispatch_lft_v2(const LftArgs<double>& a, hipStream_t stream) {
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), bytes, stream, args);
     return hipGetLastError();
   };
-  // conditioned kernel, then the rerun launch (cond = 1) of the flagged problems
-  // developer builds under HOP_OPT_NO_RERUN: the flagged problems' status also
-  // carries the first failing test and horizon (bits 5.., lft_cond_cf_kernel)
-  const int why_bit = (kDevBuild && opt(HOP_OPT_NO_RERUN)) ? 4 : 0;
-  auto cond_rerun = [&](auto kc, auto kr, size_t bytes, bool rerun) {
-    LftArgs<double> c = a;
-    const bool force = opt(HOP_OPT_FORCE_HANDOVER);
-    c.cond = (force ? 2 : 0) | why_bit;
-    hipError_t e = launch(kc, bytes, c);
-    if (e != hipSuccess || !rerun) return e;
-    // the rerun launch: non-finite triage, then the recompute of the rest
-    // (HOP_OPT_NO_RERUN: the triage alone, the rest keep HOP_ST_HANDOVER)
-    LftArgs<double> r = a;
-    r.cond = 1 | (force ? 16 : 0) | (opt(HOP_OPT_NO_RERUN) ? 8 | why_bit : 0);
-    return launch(kr, bytes, r);
+  // the launch pair of the s = 13 fp64 paths (kCondPolicyS13, hop_kernels.hpp): the
+  // conditioned kernel kc, then the rerun launch kr (non-finite triage, recompute of the
+  // flagged problems, in bytes_r of LDS if given); rerun = false: kc alone (A/B timing).
+  // Developer builds under HOP_OPT_NO_RERUN: the flagged problems' status also carries
+  // the first failing test and horizon (bits 5.., lft_cond_cf_kernel)
+  auto cond_rerun = [&](auto kc, auto kr, size_t bytes, bool rerun, size_t bytes_r = 0) {
+    CondPolicy p = kCondPolicyS13;
+    p.rerun = rerun;
+    return launch_cond_pair(
+        a, p, [&](const LftArgs<double>& c) { return launch(kc, bytes, c); },
+        [&](const LftArgs<double>& r) { return launch(kr, bytes_r ? bytes_r : bytes, r); });
   };
   // augmented blocks: the rerun launch is the pipelined recompute (lft_rerun_pipe_kernel;
   // its LDS also holds the LFT body's layout for the fallback)
@@ -4066,16 +4061,6 @@ hipError_t dispatch_lft_v2(const LftArgs<double>& a, hipStream_t stream) {
           ? (size_t)PipeG::BYTES
           : (size_t)v2::Geo<13, 4>::WAVE_BYTES * kWavesPerBlock;
   static_assert(bytes_pipe <= 160 * 1024, "one workgroup per CU");
-  auto cond_pipe = [&](auto kc, size_t bytes) {
-    LftArgs<double> c = a;
-    const bool force = opt(HOP_OPT_FORCE_HANDOVER);
-    c.cond = (force ? 2 : 0) | why_bit;
-    hipError_t e = launch(kc, bytes, c);
-    if (e != hipSuccess) return e;
-    LftArgs<double> r = a;
-    r.cond = 1 | (force ? 16 : 0) | (opt(HOP_OPT_NO_RERUN) ? 8 | why_bit : 0);
-    return launch(v2::lft_rerun_pipe_kernel<v2::SchedLdlDma, 13, 4, v2::kPipeBS>, bytes_pipe, r);
-  };
   if (a.traj) {  // in-kernel augmentation (capi routes only s = 13, m = 4 here)
     if (a.s != 13 || a.m != 4 || a.tr.n != 12 || a.tr.m != 4) return hipErrorNotSupported;
     const size_t bytes = (size_t)(v2::Geo<13, 4>::WAVE_BYTES_T * kWavesPerBlock);
@@ -4100,9 +4085,8 @@ hipError_t dispatch_lft_v2(const LftArgs<double>& a, hipStream_t stream) {
     if (variant == 24 || opt(HOP_OPT_STAMPS))  // section stamps (tools/stamps.py --traj)
       return launch(v2::lft_sweep_v2_kernel<v2::SchedLdlTrajStamped, 13, 4>, bytes, a);
     if (variant == 61) {  // the fused hand-over (measured slower)
-      LftArgs<double> c = a;
-      c.cond = opt(HOP_OPT_FORCE_HANDOVER) ? 2 : 0;
-      return launch(v2::lft_cond_cf_kernel<v2::SchedCondTrajF, 13, 4>, bytes, c);
+      return launch(v2::lft_cond_cf_kernel<v2::SchedCondTrajF, 13, 4>, bytes,
+                    with_cond(a, cond_first_word(kCondPolicyFused)));
     }
 #endif
     // default: closed-form stage inverses, then the pipelined rerun
@@ -4112,14 +4096,9 @@ hipError_t dispatch_lft_v2(const LftArgs<double>& a, hipStream_t stream) {
                                       ? (size_t)PipeT::BYTES
                                       : (size_t)v2::Geo<13, 4>::WAVE_BYTES_T * kWavesPerBlock;
       static_assert(bytes_pt <= 160 * 1024, "one workgroup per CU");
-      LftArgs<double> c = a;
-      const bool force = opt(HOP_OPT_FORCE_HANDOVER);
-      c.cond = (force ? 2 : 0) | why_bit;
-      const hipError_t e = launch(v2::lft_cond_cf_kernel<v2::SchedCondTraj, 13, 4>, bytes, c);
-      if (e != hipSuccess) return e;
-      LftArgs<double> r = a;
-      r.cond = 1 | (force ? 16 : 0) | (opt(HOP_OPT_NO_RERUN) ? 8 | why_bit : 0);
-      return launch(v2::lft_rerun_pipe_kernel<v2::SchedLdlTraj, 13, 4, v2::kPipeBS>, bytes_pt, r);
+      return cond_rerun(v2::lft_cond_cf_kernel<v2::SchedCondTraj, 13, 4>,
+                        v2::lft_rerun_pipe_kernel<v2::SchedLdlTraj, 13, 4, v2::kPipeBS>, bytes,
+                        true, bytes_pt);
     }
   }
   if (a.s <= 5) return dispatch_cond_small(a, stream);  // (lft_small.hip when not taken)
@@ -4178,9 +4157,8 @@ hipError_t dispatch_lft_v2(const LftArgs<double>& a, hipStream_t stream) {
     case 60: {  // fused hand-over: flagged problems recomputed at the end of the same
                 // launch (lft_v2_body); the kernel then carries the LFT body's scratch and
                 // measured 0.7-2 % slower than the default's second launch
-      LftArgs<double> c = a;
-      c.cond = opt(HOP_OPT_FORCE_HANDOVER) ? 2 : 0;
-      return launch(v2::lft_cond_kernel<v2::SchedCondLSymF, 13, 4>, bytes, c);
+      return launch(v2::lft_cond_kernel<v2::SchedCondLSymF, 13, 4>, bytes,
+                    with_cond(a, cond_first_word(kCondPolicyFused)));
     }
     case 2: return launch(v2::lft_sweep_v2_kernel<v2::Select, 13, 4>, bytes, a);
     case 8: return launch(v2::lft_sweep_v2_kernel<v2::Chain, 13, 4>, bytes, a);
@@ -4202,22 +4180,19 @@ hipError_t dispatch_lft_v2(const LftArgs<double>& a, hipStream_t stream) {
   constexpr bool pack1 = false, pack2 = false;
 #endif
   if (!pack1 && (pack2 || (a.batch + kProbPerWave - 1) / kProbPerWave > 4ll * cu_count(stream))) {
-    LftArgs<double> c = a;
-    const bool force = opt(HOP_OPT_FORCE_HANDOVER);
-    c.cond = (force ? 2 : 0) | why_bit;
-    hipError_t e = launch(v2::lft_cond_kernel<v2::SchedCondLSymP, 13, 4>,
-                          (size_t)v2::Geo<13, 4, 8, true>::WAVE_BYTES * kWavesPerBlock, c);
-    if (e != hipSuccess) return e;
-    LftArgs<double> r = a;  // as cond_pipe: triage, then the pipelined recompute
-    r.cond = 1 | (force ? 16 : 0) | (opt(HOP_OPT_NO_RERUN) ? 8 | why_bit : 0);
-    return launch(v2::lft_rerun_pipe_kernel<v2::SchedLdlDma, 13, 4, v2::kPipeBS>, bytes_pipe, r);
+    return cond_rerun(v2::lft_cond_kernel<v2::SchedCondLSymP, 13, 4>,
+                      v2::lft_rerun_pipe_kernel<v2::SchedLdlDma, 13, 4, v2::kPipeBS>,
+                      (size_t)v2::Geo<13, 4, 8, true>::WAVE_BYTES * kWavesPerBlock, true,
+                      bytes_pipe);
   }
   // default (variant 40): conditioned prefix + rerun of the problems it flagged; the
   // stage / terminal inverses of the unhalved symmetric sums (SYM2: 1-2 % faster than
   // the halved sums, profiles/history/r03_ab1_cond_schedules.txt, r03_ab_pe.txt); the periodic
   // symmetrisation after the step's DMA issue, in its own LDS scratch (SchedCondLSymL:
   // 0.4 % faster than before it, bitwise equal, profiles/history/r04_p18_ab_symlate.txt)
-  return cond_pipe(v2::lft_cond_kernel<v2::SchedCondLSymL, 13, 4>, bytes_symlate);
+  return cond_rerun(v2::lft_cond_kernel<v2::SchedCondLSymL, 13, 4>,
+                    v2::lft_rerun_pipe_kernel<v2::SchedLdlDma, 13, 4, v2::kPipeBS>, bytes_symlate,
+                    true, bytes_pipe);
 }
 
 }  // namespace hop
@@ -4235,28 +4210,25 @@ hipError_t dispatch_lft_v2_f32(const LftArgs<float>& a, hipStream_t stream) {
     return hipErrorNotSupported;
   using G = v2::Geo<13, 4, 4>;
   const long long blocks = (a.batch + kProbPerBlock - 1) / kProbPerBlock;
-  LftArgs<float> c = a;
-  c.cond = opt(HOP_OPT_FORCE_HANDOVER) ? 2 : 0;
+  auto first = [&](const LftArgs<float>& c) {
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256),
+                         (size_t)(G::WAVE_BYTES * kWavesPerBlock), stream, c);
+      return hipGetLastError();
+    };
 #ifdef HOP_DEV
-  if (var == 56 || var == 57)  // the predict on the f32 matrix cores (SchedCondMfma)
-    hipLaunchKernelGGL((v2::lft_cond_kernel<v2::SchedCondMfma, 13, 4, float>),
-                       dim3((unsigned)blocks), dim3(256), (size_t)(G::WAVE_BYTES * kWavesPerBlock),
-                       stream, c);
-  else
+    if (var == 56 || var == 57)  // the predict on the f32 matrix cores (SchedCondMfma)
+      return go(v2::lft_cond_kernel<v2::SchedCondMfma, 13, 4, float>);
+    if (var == 95)  // plain converting reads (the round-2 fp32-block kernel, A/B)
+      return go(v2::lft_cond_kernel<v2::SchedCond, 13, 4, float>);
 #endif
-#ifdef HOP_DEV
-  if (var == 95)  // plain converting reads (the round-2 fp32-block kernel, A/B)
-    hipLaunchKernelGGL((v2::lft_cond_kernel<v2::SchedCond, 13, 4, float>), dim3((unsigned)blocks),
-                       dim3(256), (size_t)(G::WAVE_BYTES * kWavesPerBlock), stream, c);
-  else
-#endif
-  // QT / A / B reads under the two sweeps (SchedCondL: the fp64 default's placement)
-  hipLaunchKernelGGL((v2::lft_cond_kernel<v2::SchedCondL, 13, 4, float>), dim3((unsigned)blocks),
-                     dim3(256), (size_t)(G::WAVE_BYTES * kWavesPerBlock), stream, c);
-  if (var == 41 || var == 57 || opt(HOP_OPT_NO_RERUN)) return hipGetLastError();
-  LftArgs<float> r = a;
-  r.cond = 1;
-  return dispatch_lft<float>(r, stream);
+    // QT / A / B reads under the two sweeps (SchedCondL: the fp64 default's placement)
+    return go(v2::lft_cond_kernel<v2::SchedCondL, 13, 4, float>);
+  };
+  CondPolicy p = kCondPolicyPlain;
+  p.rerun = var != 41 && var != 57;  // 41, 57: the conditioned kernel alone (A/B timing)
+  return launch_cond_pair(a, p, first,
+                          [&](const LftArgs<float>& r) { return dispatch_lft<float>(r, stream); });
 }
 }  // namespace hop
 
