@@ -126,6 +126,30 @@ WIDE_JCURVE_SIGNATURES = {
     "hop_bruteforce_jcurve_wide_f64": (C.c_int, _JC64),
 }
 
+# include/hop_chain.h (the mass-spring chain as a device system); bound beside the others.
+# Every entry starts with a pointer to ChainParams; the rest mirrors the narrow entry's list
+# (cost: xg bs u_ref bs Q R Qf w bs)
+_CCOST = [_P, _I64, _P, _I64, _P, _P, _P, _P, _I64]
+CHAIN_SIGNATURES = {
+    "hop_chain_dynamics_f64": (C.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _I64, _P]),
+    "hop_chain_rollout_f64": (C.c_int, [_P, _P, _I64, _P, _I64, _I32, C.c_double, _P, _P]),
+    "hop_chain_linearize_f64": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, C.c_double,
+                                          C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
+    "hop_chain_cost_true_f64": (C.c_int, [_P, _P, _P, _P] + _CCOST + [_I64, _I32, _P, _P]),
+    "hop_chain_forward_workspace_bytes": (C.c_size_t, [_P, _I64, _I32, _I32]),
+    "hop_chain_forward_linesearch_f64": (C.c_int, [_P, _P, _P] + _CCOST +
+                                         [_P, _P, _P, _P, _P, _I32, _I64, _I32, _P, C.c_size_t,
+                                          _P, _P, _P, _P, _P, _P]),
+}
+CHAIN_MAX_P = 15  # include/hop_chain.h HOP_CHAIN_MAX_P
+
+
+class ChainParams(C.Structure):
+    """hop_chain_params (include/hop_chain.h)."""
+    _fields_ = [("p", _I32), ("m", _I32), ("dt", C.c_double), ("k", C.c_double),
+                ("ks", C.c_double), ("c", C.c_double)]
+
+
 _lock = threading.Lock()
 _lib = None
 
@@ -152,7 +176,8 @@ def load(path: str | None = None):
         lib = C.CDLL(p)
         other = path is not None or "HOP_LIB" in os.environ
         for name, (res, args) in (list(SIGNATURES.items()) + list(WIDE_SIGNATURES.items())
-                                  + list(WIDE_JCURVE_SIGNATURES.items())):
+                                  + list(WIDE_JCURVE_SIGNATURES.items())
+                                  + list(CHAIN_SIGNATURES.items())):
             if other and not hasattr(lib, name):
                 continue  # an older build loaded for an A/B (tools/ab_libs.py, HOP_LIB)
             fn = getattr(lib, name)

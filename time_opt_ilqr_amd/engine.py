@@ -805,8 +805,49 @@ SYSTEM_IDS = {"double_integrator": 0, "di": 0, "cartpole": 1, "quadrotor": 2, "p
               "segway": 4}
 
 
+def is_chain(system) -> bool:
+    """True for a systems.SpringChain: the device system whose size is a run-time
+    argument (include/hop_chain.h); dynamics, rollout, linearize, cost_true and
+    forward_linesearch take it as ``system`` and step with its own dt."""
+    return getattr(system, "chain_params", None) is not None
+
+
+def _chain_params(system):
+    p, m, dt, k, ks, c = system.chain_params()
+    return _lib.ChainParams(int(p), int(m), float(dt), float(k), float(ks), float(c))
+
+
+def _chain_cost_args(cost, Bn, n, m, dev):
+    """hop_chain.h's cost arguments (xg bs u_ref bs Q R Qf w bs) of a CostParams."""
+    torch = _torch()
+    if cost.obstacles is not None and len(cost.obstacles):
+        raise ValueError("a spring chain takes no obstacle table (it has no planar position)")
+    if cost.wrap_idx is not None and len(cost.wrap_idx):
+        raise ValueError("a spring chain has no angle states: wrap_idx must be empty")
+    dt = torch.float64
+    xg = _dev(cost.xg, "xg", dt, dev)
+    u_ref = _dev(cost.u_ref, "u_ref", dt, dev)
+    Q, R, Qf = (_dev(t, nm, dt, dev) for t, nm in ((cost.Q, "Q"), (cost.R, "R"), (cost.Qf, "Qf")))
+    w = _scalar_or_vec(cost.w, dt, dev, "w")
+    for t, nm, shp in ((Q, "Q", (n, n)), (R, "R", (m, m)), (Qf, "Qf", (n, n))):
+        if tuple(t.shape) != shp:
+            raise ValueError(f"spring chain: {nm} must be one {shp} block shared by the batch, "
+                             f"got {tuple(t.shape)}")
+    for t, nm, shp in ((xg, "xg", (n,)), (u_ref, "u_ref", (m,))):
+        if tuple(t.shape[-1:]) != shp:
+            raise ValueError(f"{nm} must end in {shp}, got {tuple(t.shape)}")
+    if w.numel() not in (1, Bn):
+        raise ValueError("w must be a scalar or [B]")
+    args = [_lib.ptr(xg), _bstride(xg, 1, "xg", Bn), _lib.ptr(u_ref),
+            _bstride(u_ref, 1, "u_ref", Bn), _lib.ptr(Q), _lib.ptr(R), _lib.ptr(Qf),
+            _lib.ptr(w), 0 if w.numel() == 1 else 1]
+    return args, (xg, u_ref, Q, R, Qf, w)
+
+
 def system_dims(system) -> tuple:
-    """(n, m) of a system id or name (hop_system_dims)."""
+    """(n, m) of a system id or name (hop_system_dims), or of a spring chain."""
+    if is_chain(system):
+        return int(system.n), int(system.m)
     sid = system_id(system)
     n, m = _lib.C.c_int32(), _lib.C.c_int32()
     _lib.check(_lib.load().hop_system_dims(sid, _lib.C.byref(n), _lib.C.byref(m)))
@@ -851,11 +892,14 @@ def linearize(system, X, U, dt: float, *, central: bool = False, n_use: Optional
     U = _dev(U, "U", torch.float64, X.device)
     if X.dim() == 2:  # one problem [N+1, n]: a batch of one (both layouts)
         X, U = X[None], U[None]
+    chain = is_chain(system)
     if tile64:
+        if chain:
+            raise ValueError("a spring chain has no tile64 outputs (batch-major fp64 only)")
         return _linearize_tile64(system, X, U, dt, central, n_use, epsx, epsu, relx, relu,
                                  tile64_dtype or torch.float64)
-    sid = system_id(system)
-    n, m = system_dims(sid)
+    sid = getattr(system, "name", "chain") if chain else system_id(system)
+    n, m = system_dims(system if chain else sid)
     if X.dim() != 3 or U.dim() != 3 or X.shape[-1] != n or U.shape[-1] != m:
         raise ValueError(f"X must be [B, N+1, {n}] and U [B, N, {m}] for system {sid}")
     Bn, N = U.shape[0], U.shape[1]
@@ -869,10 +913,13 @@ def linearize(system, X, U, dt: float, *, central: bool = False, n_use: Optional
     Bm = torch.empty((Bn, N, n, m), dtype=torch.float64, device=dev)
     a_res = torch.empty((Bn, N, n), dtype=torch.float64, device=dev)
     Fx = torch.empty((Bn, N, n), dtype=torch.float64, device=dev) if want_fx else None
-    rc = _lib.load().hop_linearize_f64(sid, float(dt), _lib.ptr(X), _lib.ptr(U), Bn, N, n_use,
-                                       int(bool(central)), float(epsx), float(epsu), float(relx),
-                                       float(relu), _lib.ptr(A), _lib.ptr(Bm), _lib.ptr(a_res),
-                                       _lib.ptr(Fx), _lib.stream_handle(dev))
+    tail = (Bn, N, n_use, int(bool(central)), float(epsx), float(epsu), float(relx), float(relu),
+            _lib.ptr(A), _lib.ptr(Bm), _lib.ptr(a_res), _lib.ptr(Fx), _lib.stream_handle(dev))
+    if chain:
+        rc = _lib.load().hop_chain_linearize_f64(_lib.C.byref(_chain_params(system)), _lib.ptr(X),
+                                                 _lib.ptr(U), *tail)
+    else:
+        rc = _lib.load().hop_linearize_f64(sid, float(dt), _lib.ptr(X), _lib.ptr(U), *tail)
     _lib.check(rc)
     return Linearization(A, Bm, a_res, Fx, n_use=n_use)
 
@@ -913,16 +960,20 @@ def _linearize_tile64(system, X, U, dt, central, n_use, epsx, epsu, relx, relu, 
 def dynamics(system, X, U, dt: float):
     """x' = F(x, u) for X [..., n], U [..., m] (fp64, on the device)."""
     torch = _torch()
-    sid = system_id(system)
-    n, m = system_dims(sid)
+    chain = is_chain(system)
+    sid = None if chain else system_id(system)
+    n, m = system_dims(system if chain else sid)
     X = _dev(X, "X", torch.float64)
     U = _dev(U, "U", torch.float64, X.device)
     if X.shape[-1] != n or U.shape[-1] != m or X.shape[:-1] != U.shape[:-1]:
         raise ValueError(f"X [..., {n}] and U [..., {m}] with the same leading shape expected")
     cnt = X.numel() // n
     out = torch.empty_like(X)
-    rc = _lib.load().hop_dynamics_f64(sid, float(dt), _lib.ptr(X), n, _lib.ptr(U), m, cnt,
-                                      _lib.ptr(out), n, _lib.stream_handle(X.device))
+    tail = (_lib.ptr(X), n, _lib.ptr(U), m, cnt, _lib.ptr(out), n, _lib.stream_handle(X.device))
+    if chain:
+        rc = _lib.load().hop_chain_dynamics_f64(_lib.C.byref(_chain_params(system)), *tail)
+    else:
+        rc = _lib.load().hop_dynamics_f64(sid, float(dt), *tail)
     _lib.check(rc)
     return out
 
@@ -977,7 +1028,7 @@ class CostParams:
 
 
 def _traj_xu(system, X, U):
-    sid = system_id(system)
+    sid = system if is_chain(system) else system_id(system)  # a chain stays the object
     n, m = system_dims(sid)
     torch = _torch()
     X = _dev(X, "X", torch.float64)
@@ -992,7 +1043,8 @@ def _traj_xu(system, X, U):
 def rollout(system, x0, U, dt: float, *, max_state_norm: float = 1e6):
     """Batched rollout (solver.py:42-62): x0 [n] or [B, n], U [B, N, m] -> X [B, N+1, n]."""
     torch = _torch()
-    sid = system_id(system)
+    chain = is_chain(system)
+    sid = system if chain else system_id(system)
     n, m = system_dims(sid)
     U = _dev(U, "U", torch.float64)
     dev = U.device
@@ -1004,8 +1056,12 @@ def rollout(system, x0, U, dt: float, *, max_state_norm: float = 1e6):
         raise ValueError(f"x0 must be [{n}] or [B, {n}]")
     X = torch.empty((Bn, N + 1, n), dtype=torch.float64, device=dev)
     x_bs = n if (x0.dim() == 2 and x0.shape[0] == Bn and Bn > 1) else 0
-    rc = _lib.load().hop_rollout_f64(sid, float(dt), _lib.ptr(x0), x_bs, _lib.ptr(U), Bn, N,
-                                     float(max_state_norm), _lib.ptr(X), _lib.stream_handle(dev))
+    tail = (_lib.ptr(x0), x_bs, _lib.ptr(U), Bn, N, float(max_state_norm), _lib.ptr(X),
+            _lib.stream_handle(dev))
+    if chain:
+        rc = _lib.load().hop_chain_rollout_f64(_lib.C.byref(_chain_params(system)), *tail)
+    else:
+        rc = _lib.load().hop_rollout_f64(sid, float(dt), *tail)
     _lib.check(rc)
     return X
 
@@ -1017,10 +1073,16 @@ def cost_true(system, X, U, T_star, cost: CostParams):
     Bn, N = U.shape[0], U.shape[1]
     T = _dev(torch.as_tensor(T_star, device=dev).to(torch.int32).reshape(-1).expand(Bn),
              "T_star")
-    cargs, keep = cost.args(Bn, n, m, dev)
     J = torch.empty((Bn,), dtype=torch.float64, device=dev)
-    rc = _lib.load().hop_cost_true_f64(sid, _lib.ptr(X), _lib.ptr(U), _lib.ptr(T), *cargs, Bn, N,
-                                       _lib.ptr(J), _lib.stream_handle(dev))
+    if is_chain(sid):
+        cargs, keep = _chain_cost_args(cost, Bn, n, m, dev)
+        rc = _lib.load().hop_chain_cost_true_f64(
+            _lib.C.byref(_chain_params(sid)), _lib.ptr(X), _lib.ptr(U), _lib.ptr(T), *cargs, Bn, N,
+            _lib.ptr(J), _lib.stream_handle(dev))
+    else:
+        cargs, keep = cost.args(Bn, n, m, dev)
+        rc = _lib.load().hop_cost_true_f64(sid, _lib.ptr(X), _lib.ptr(U), _lib.ptr(T), *cargs, Bn,
+                                           N, _lib.ptr(J), _lib.stream_handle(dev))
     _lib.check(rc)
     del keep
     return J
@@ -1054,20 +1116,27 @@ def forward_linesearch(system, X, U, T_star, K, k, cost: CostParams, dt: float, 
     al = [float(a) for a in alphas]
     if not 1 <= len(al) <= 8:
         raise ValueError("1..8 step sizes")
-    cargs, keep = cost.args(Bn, n, m, dev)
+    chain = is_chain(sid)
     lib = _lib.load()
-    ws_bytes = int(lib.hop_forward_workspace_bytes(sid, Bn, N, len(al)))
+    if chain:
+        cp = _chain_params(sid)
+        cargs, keep = _chain_cost_args(cost, Bn, n, m, dev)
+        ws_bytes = int(lib.hop_chain_forward_workspace_bytes(_lib.C.byref(cp), Bn, N, len(al)))
+    else:
+        cargs, keep = cost.args(Bn, n, m, dev)
+        ws_bytes = int(lib.hop_forward_workspace_bytes(sid, Bn, N, len(al)))
     ws = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=dev)
     out = LineSearchResult(torch.empty_like(X), torch.empty_like(U),
                            torch.empty((Bn,), dtype=torch.float64, device=dev),
                            torch.empty((Bn,), dtype=torch.float64, device=dev),
                            torch.empty((Bn,), dtype=torch.int32, device=dev))
     c_al = (_lib.C.c_double * len(al))(*al)
-    rc = lib.hop_forward_linesearch_f64(
-        sid, float(dt), _lib.ptr(X), _lib.ptr(U), *cargs, _lib.ptr(T), _lib.ptr(act),
-        _lib.ptr(K), _lib.ptr(k), c_al, len(al), Bn, N, _lib.C.c_void_p(ws.data_ptr()),
-        ws_bytes, _lib.ptr(out.X), _lib.ptr(out.U), _lib.ptr(out.J), _lib.ptr(out.J_old),
-        _lib.ptr(out.accepted), _lib.stream_handle(dev))
+    head = (_lib.C.byref(cp),) if chain else (sid, float(dt))
+    fn = lib.hop_chain_forward_linesearch_f64 if chain else lib.hop_forward_linesearch_f64
+    rc = fn(*head, _lib.ptr(X), _lib.ptr(U), *cargs, _lib.ptr(T), _lib.ptr(act),
+            _lib.ptr(K), _lib.ptr(k), c_al, len(al), Bn, N, _lib.C.c_void_p(ws.data_ptr()),
+            ws_bytes, _lib.ptr(out.X), _lib.ptr(out.U), _lib.ptr(out.J), _lib.ptr(out.J_old),
+            _lib.ptr(out.accepted), _lib.stream_handle(dev))
     _lib.check(rc)
     ws.record_stream(torch.cuda.current_stream(dev))
     del keep

@@ -7,7 +7,8 @@
 Same names, arguments and return shapes (lists of per-step NumPy blocks) for one
 trajectory; ``linearize_batch`` is the batched device form (torch tensors in
 HBM, the layout engine.propagate_traj / engine.riccati read).  ``F`` must be a
-:class:`~time_opt_ilqr_amd.systems.DeviceDynamics` (a system the kernel knows):
+:class:`~time_opt_ilqr_amd.systems.DeviceDynamics` or
+:class:`~time_opt_ilqr_amd.systems.SpringChain` (a system the kernel knows):
 an arbitrary Python callable is refused with TypeError rather than evaluated on
 the CPU.
 """
@@ -16,14 +17,18 @@ from __future__ import annotations
 import numpy as np
 
 from . import engine
-from .systems import DeviceDynamics
+from .systems import DeviceDynamics, SpringChain
 
 
 def _check_F(F):
-    if not isinstance(F, DeviceDynamics):
+    if not isinstance(F, (DeviceDynamics, SpringChain)):
         raise TypeError("F must be a time_opt_ilqr_amd.systems DeviceDynamics (the device "
                         "linearisation has no path for arbitrary Python dynamics)")
     return F
+
+
+def _sys(F):
+    return F if engine.is_chain(F) else F.system_id
 
 
 def _run(F, X, U, central, epsx, epsu, relx, relu):
@@ -39,7 +44,7 @@ def _run(F, X, U, central, epsx, epsu, relx, relu):
     if Xt.shape[0] < N + 1:  # the linearisations only read X[:N]
         Xt = torch.cat([Xt, Xt[-1:].expand(N + 1 - Xt.shape[0], -1)], 0)
     Ut = torch.as_tensor(np.ascontiguousarray(U), device=dev)
-    return engine.linearize(F.system_id, Xt[None], Ut[None], F.dt, central=central,
+    return engine.linearize(_sys(F), Xt[None], Ut[None], F.dt, central=central,
                             epsx=epsx, epsu=epsu, relx=relx, relu=relu)
 
 
@@ -76,5 +81,5 @@ def linearize_batch(F, X, U, *, central: bool = False, n_use=None, epsx: float =
     """Batched form: X [B, N+1, n], U [B, N, m] fp64 device tensors ->
     engine.Linearization(A [B, N, n, n], B [B, N, n, m], a_res [B, N, n])."""
     F = _check_F(F)
-    return engine.linearize(F.system_id, X, U, F.dt, central=central, n_use=n_use, epsx=epsx,
+    return engine.linearize(_sys(F), X, U, F.dt, central=central, n_use=n_use, epsx=epsx,
                             epsu=epsu, relx=relx, relu=relu, want_fx=want_fx)

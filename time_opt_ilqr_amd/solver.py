@@ -90,7 +90,9 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
     each stage is synchronised for it -- stage_timers=False skips those syncs and
     leaves the host waiting only on the once-per-iteration "all done" flag).
 
-    ``system`` is a device system (id, name or systems.DeviceDynamics, with ``dt``) or
+    ``system`` is a device system (id, name or systems.DeviceDynamics, with ``dt``; or a
+    systems.SpringChain, which steps with its own dt and runs wide solves end to end on
+    the device) or
     a host_dynamics.HostDynamics wrapping a Python callable F(x, u): then the rollouts,
     the FD linearisation and the line search evaluate F on the host per problem (the
     reference's own call form, host_dynamics.py) and the select, Riccati and accept
@@ -111,7 +113,14 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
         if extra_stage_cost is not None:
             raise ValueError("device dynamics take the point-mass obstacles table; a "
                              "Python extra_stage_cost needs host dynamics")
-        sid = engine.system_id(system)
+        if engine.is_chain(system):  # a systems.SpringChain: the object is the system
+            if obstacles is not None and len(obstacles) > 0:
+                raise ValueError("a spring chain takes no obstacle table")
+            if wrap_idx is not None and len(wrap_idx) > 0:
+                raise ValueError("a spring chain has no angle states: wrap_idx must be empty")
+            sid, dt = system, float(system.dt)  # it steps with its own dt
+        else:
+            sid = engine.system_id(system)
         n, m = engine.system_dims(sid)
     dev = device or torch.device("cuda", torch.cuda.current_device())
     f64 = torch.float64
@@ -351,16 +360,21 @@ def _host_linesearch(system, Xh, Uh, T_star, K, k, active, cost_np, alphas, extr
 # ---------------------------------------------------------------------------
 
 def _dyn(F):
-    from .systems import DeviceDynamics
-    if not isinstance(F, DeviceDynamics):
-        raise TypeError("F must be a time_opt_ilqr_amd.systems.DeviceDynamics "
+    from .systems import DeviceDynamics, SpringChain
+    if not isinstance(F, (DeviceDynamics, SpringChain)):
+        raise TypeError("F must be a time_opt_ilqr_amd.systems.DeviceDynamics or SpringChain "
                         "(use the systems.make_* makers)")
     return F
 
 
+def _sys(F):
+    """what the engine takes as ``system``: a built-in system's id, a SpringChain itself"""
+    return F if engine.is_chain(F) else F.system_id
+
+
 def _on_device(F) -> bool:
-    from .systems import DeviceDynamics
-    if isinstance(F, DeviceDynamics):
+    from .systems import DeviceDynamics, SpringChain
+    if isinstance(F, (DeviceDynamics, SpringChain)):
         return True
     if not callable(F):
         raise TypeError("F must be a systems.DeviceDynamics or a callable F(x, u) -> x_next")
@@ -415,7 +429,7 @@ def rollout(F, x0: np.ndarray, U: np.ndarray, *, max_state_norm: float = 1e6) ->
     if not _on_device(F):
         return host_dynamics.rollout(F, x0, U, max_state_norm=max_state_norm)
     F = _dyn(F)
-    X = engine.rollout(F.system_id, _t(np.asarray(x0, dtype=float).reshape(-1)), _t(U)[None],
+    X = engine.rollout(_sys(F), _t(np.asarray(x0, dtype=float).reshape(-1)), _t(U)[None],
                        F.dt, max_state_norm=max_state_norm)
     return X[0].cpu().numpy()
 
@@ -447,6 +461,8 @@ def cost_timeopt_true(X, U, xg, u_ref, Q, R, alpha, w, T_star, wrap_idx=None,
 
 
 def _system_for(system, n, m):
+    if engine.is_chain(system):
+        return system
     if system is not None:
         return engine.system_id(getattr(system, "system_id", system))
     cands = [s for s in range(5) if engine.system_dims(s) == (n, m)]
@@ -482,7 +498,7 @@ def forward_linesearch_fixedT(F, X, U, xg, u_ref, Q, R, alpha, w, T_star, k_list
         return Xn, Un, float(J), acc >= 0
     F = _dyn(F)
     cost = _cost_params(X, xg, u_ref, Q, R, alpha, w, wrap_idx, extra_stage_cost)
-    r = engine.forward_linesearch(F.system_id, _t(X[:N + 1])[None], _t(U)[None], [T],
+    r = engine.forward_linesearch(_sys(F), _t(X[:N + 1])[None], _t(U)[None], [T],
                                   _t(K)[None], _t(k)[None], cost, F.dt, alphas=alphas)
     acc = int(r.accepted[0].item()) >= 0
     if not acc:
@@ -506,7 +522,7 @@ def ilqr_timeopt(F, x0, xg, u_ref, Q, R, alpha, w, N: int, T_min: int, T_max: in
     n = x0.shape[1]
     if _on_device(F) and _is_obstacle_cost(extra_stage_cost):
         F = _dyn(F)
-        system, kw = F.system_id, dict(dt=F.dt, obstacles=_obstacle_rows(extra_stage_cost))
+        system, kw = _sys(F), dict(dt=F.dt, obstacles=_obstacle_rows(extra_stage_cost))
     else:  # a Python callable (dynamics or stage cost): evaluated on the host per problem
         m = np.atleast_2d(np.asarray(R, dtype=float)).shape[0]
         if isinstance(F, host_dynamics.HostDynamics):

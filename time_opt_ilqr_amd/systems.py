@@ -108,6 +108,89 @@ def make_segway_balance(dt: float = 0.02, N: int = 240):
             np.diag([20.0, 2.0, 250.0, 10.0]), 1e-4, N, 40, 200, [2], None)
 
 
+@dataclass(frozen=True)
+class SpringChain:
+    """The mass-spring chain as a device system (include/hop_chain.h, csrc/chain.hip):
+    x = [q (p positions), v (p velocities)], unit masses between two fixed ends, spring
+    force k d + ks sin(d) on the stretch d, damping c, input j on mass j * p // m, one
+    explicit Euler step of dt.  Its size is a run-time argument (1 <= m <= p <= 15, so up
+    to 30 states): the engine and solver functions take the object itself as ``system`` /
+    ``F`` and step with its own dt."""
+    p: int
+    m: int
+    dt: float = 0.1
+    k: float = 2.0
+    ks: float = 0.5
+    c: float = 0.3
+    n: int = 0          # 2 p (filled in)
+    name: str = "spring_chain"
+
+    def __post_init__(self):
+        if not 1 <= int(self.p) <= 15 or not 1 <= int(self.m) <= int(self.p):
+            raise ValueError("SpringChain needs 1 <= m <= p <= 15")
+        if self.n not in (0, 2 * int(self.p)):
+            raise ValueError("SpringChain: n is 2 p")
+        if not float(self.dt) > 0.0:
+            raise ValueError("SpringChain: dt must be positive")
+        object.__setattr__(self, "n", 2 * int(self.p))
+
+    def chain_params(self):
+        """(p, m, dt, k, ks, c): what the hop_chain_* entries take."""
+        return int(self.p), int(self.m), float(self.dt), float(self.k), float(self.ks), \
+            float(self.c)
+
+    def __call__(self, x, u):
+        """One step for one (x, u) pair, NumPy in / NumPy out (reference call form)."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        xt = torch.as_tensor(np.asarray(x, dtype=float).reshape(self.n), device=dev)
+        ut = torch.as_tensor(np.asarray(u, dtype=float).reshape(self.m), device=dev)
+        return engine.dynamics(self, xt, ut, self.dt).cpu().numpy()
+
+    def batch(self, X, U):
+        """x' for device tensors X [..., n], U [..., m]."""
+        return engine.dynamics(self, X, U, self.dt)
+
+    def host(self):
+        """The same chain as a host_dynamics.HostDynamics(vectorized=True): the NumPy
+        expressions of tests/golden/make_golden_wide.py's chain_dynamics on stacked rows
+        (x [K, n], u [K, m] -> [K, n]), evaluated on the host."""
+        from .host_dynamics import HostDynamics
+        p, m, dt, k, ks, c = self.chain_params()
+        act = [j * p // m for j in range(m)]
+
+        def F(x, u):
+            x = np.asarray(x, dtype=float)
+            u = np.asarray(u, dtype=float)
+            one = x.ndim == 1
+            x, u = x.reshape(-1, 2 * p), u.reshape(-1, m)
+            q, v = x[:, :p], x[:, p:]
+            z = np.zeros((x.shape[0], 1))
+            d = np.diff(np.concatenate((z, q, z), axis=1), axis=1)
+            f = k * d + ks * np.sin(d)
+            acc = f[:, 1:] - f[:, :-1] - c * v
+            for j, i in enumerate(act):
+                acc[:, i] += u[:, j]
+            out = np.concatenate((q + dt * v, v + dt * acc), axis=1)
+            return out[0] if one else out
+
+        return HostDynamics(F, 2 * p, m, name=self.name + "_host", vectorized=True)
+
+
+def make_spring_chain(p: int = 12, m: int = 3, dt: float = 0.1, N: int = 60, seed: int = 0,
+                      k: float = 2.0, ks: float = 0.5, c: float = 0.3):
+    """The chain problem of tests/golden/make_golden_wide.py (problem()): a random start
+    (positions uniform in [-1, 1], velocities 0.2 N(0, 1), from ``seed``), the origin as
+    goal, Q = diag(1 on positions, 0.2 on velocities), R = 0.1 I, alpha = 20, w = 0.5,
+    T in [8, 55]."""
+    F = SpringChain(int(p), int(m), float(dt), float(k), float(ks), float(c))
+    rng = np.random.default_rng(seed)
+    x0 = np.concatenate((rng.uniform(-1.0, 1.0, p), 0.2 * rng.standard_normal(p)))
+    Q = np.diag(np.concatenate((np.full(p, 1.0), np.full(p, 0.2))))
+    return (F, x0, np.zeros(2 * p), np.zeros(m), Q, 0.1 * np.eye(m), 20.0, 0.5, N, 8,
+            min(55, N), [], None)
+
+
 MAKERS = {"double_integrator": make_double_integrator, "cartpole": make_cartpole_swingup,
           "quadrotor": make_quadrotor, "pointmass": make_pointmass_navigation,
-          "segway": make_segway_balance}
+          "segway": make_segway_balance, "spring_chain": make_spring_chain}
