@@ -7,6 +7,8 @@ Drop-in for the hot path of dmmsjtu-umich/time-opt-ilqr:
                                                                builders on the device)
   engine.linearize / engine.dynamics                           batched FD linearisation and
                                                                dynamics of the benchmark systems
+  engine.nominal_cost_curve / extend_nominal_backward /        the one-pass window method's
+    onepass_pick / onepass_rollout                             primitives (include/hop_onepass.h)
   systems.make_* / linearization.*                             reference-shaped drop-ins
   horizon_selection.propagator_all_Jt_aug, ...                 reference-shaped drop-ins
 

@@ -143,6 +143,26 @@ CHAIN_SIGNATURES = {
 }
 CHAIN_MAX_P = 15  # include/hop_chain.h HOP_CHAIN_MAX_P
 
+# include/hop_onepass.h (the one-pass window method's primitives); bound beside the others
+ONEPASS_SIGNATURES = {
+    # system X U cost T_min T_max batch N J T_bar stream
+    "hop_onepass_nominal_curve_f64": (C.c_int, [_I32, _P, _P] + _COST +
+                                      [_I32, _I32, _I64, _I32, _P, _P, _P]),
+    # system dt X U u_fill batch N S max_iter tol damping X_ext U_ext stream
+    "hop_onepass_extend_backward_f64": (C.c_int, [_I32, C.c_double, _P, _P, _P, _I64, _I32, _I32,
+                                                  _I32, C.c_double, C.c_double, _P, _P, _P]),
+    # Vxx Vx V0 X_ext x0 T_bar batch n n_ext T_min T_max S_left S_right wrap mult T_star Jw stream
+    "hop_onepass_pick_f64": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32,
+                                       _I32, _U32, C.c_double, _P, _P, _P]),
+    "hop_onepass_rollout_workspace_bytes": (C.c_size_t, [_I32, _I64, _I32, _I32]),
+    # system dt X_ext U_ext cost T_bar T_star active K k alphas n_alpha batch N S ws bytes
+    # X_new U_new J accepted stream
+    "hop_onepass_rollout_f64": (C.c_int, [_I32, C.c_double, _P, _P] + _COST +
+                                [_P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P, C.c_size_t,
+                                 _P, _P, _P, _P, _P]),
+}
+ONEPASS_MAX_WINDOW = 64  # include/hop_onepass.h HOP_ONEPASS_MAX_WINDOW
+
 
 class ChainParams(C.Structure):
     """hop_chain_params (include/hop_chain.h)."""
@@ -177,7 +197,8 @@ def load(path: str | None = None):
         other = path is not None or "HOP_LIB" in os.environ
         for name, (res, args) in (list(SIGNATURES.items()) + list(WIDE_SIGNATURES.items())
                                   + list(WIDE_JCURVE_SIGNATURES.items())
-                                  + list(CHAIN_SIGNATURES.items())):
+                                  + list(CHAIN_SIGNATURES.items())
+                                  + list(ONEPASS_SIGNATURES.items())):
             if other and not hasattr(lib, name):
                 continue  # an older build loaded for an A/B (tools/ab_libs.py, HOP_LIB)
             fn = getattr(lib, name)

@@ -1195,3 +1195,151 @@ def ilqr_select_mask(state, sel_status, ric_status):
                                           _lib.stream_handle(dev))
     _lib.check(rc)
     return active
+
+
+# ---- the one-pass window method's primitives (include/hop_onepass.h, onepass.hip)
+
+ONEPASS_ALPHAS = (1.0, 0.5, 0.25, 0.1)  # solver.py:383
+
+
+def _onepass_system(system):
+    if is_chain(system):
+        raise NotImplementedError("the one-pass primitives cover the five built-in device "
+                                  "systems (n <= 12), not the spring chain")
+    return system_id(system)
+
+
+def _int_vec(v, Bn, dev, name):
+    torch = _torch()
+    return _dev(torch.as_tensor(v, device=dev).to(torch.int32).reshape(-1).expand(Bn), name)
+
+
+def nominal_cost_curve(system, X, U, cost: CostParams, T_min: int, T_max: int):
+    """Batched nominal_cost_curve (solver.py:108-149) and the argmin after it
+    (solver.py:537): X [B, N+1, n], U [B, N, m] -> (J [B, T_max], T_bar [B] int32)."""
+    torch = _torch()
+    sid, n, m, X, U, dev = _traj_xu(_onepass_system(system), X, U)
+    Bn, N = U.shape[0], U.shape[1]
+    T_min, T_max = int(T_min), int(T_max)
+    if not 1 <= T_min <= T_max <= N:
+        raise ValueError(f"need 1 <= T_min <= T_max <= N, got {T_min}, {T_max}, {N}")
+    cargs, keep = cost.args(Bn, n, m, dev)
+    J = torch.empty((Bn, T_max), dtype=torch.float64, device=dev)
+    T_bar = torch.empty((Bn,), dtype=torch.int32, device=dev)
+    rc = _lib.load().hop_onepass_nominal_curve_f64(
+        sid, _lib.ptr(X), _lib.ptr(U), *cargs, T_min, T_max, Bn, N, _lib.ptr(J), _lib.ptr(T_bar),
+        _lib.stream_handle(dev))
+    _lib.check(rc)
+    del keep
+    return J, T_bar
+
+
+def extend_nominal_backward(system, X, U, u_fill, dt: float, S_back: int, *, max_iter: int = 6,
+                            tol: float = 1e-9, damping: float = 0.5):
+    """Batched extend_nominal_backward with the fixed-point preimage
+    (linearization.py:41-71, 109-170): X [B, N+1, n], U [B, N, m], u_fill [B, m] or [m] ->
+    (X_ext [B, S+N+1, n], U_ext [B, S+N, m]), 1 <= S_back <= 64."""
+    torch = _torch()
+    sid, n, m, X, U, dev = _traj_xu(_onepass_system(system), X, U)
+    Bn, N = U.shape[0], U.shape[1]
+    S = int(S_back)
+    if not 1 <= S <= _lib.ONEPASS_MAX_WINDOW:
+        raise ValueError(f"S_back must be in [1, {_lib.ONEPASS_MAX_WINDOW}], got {S}")
+    uf = _dev(u_fill, "u_fill", torch.float64, dev)
+    if uf.shape[-1] != m or uf.dim() > 2 or (uf.dim() == 2 and uf.shape[0] not in (1, Bn)):
+        raise ValueError(f"u_fill must be [{m}] or [B, {m}]")
+    uf = uf.reshape(-1, m).expand(Bn, m).contiguous()
+    X_ext = torch.empty((Bn, S + N + 1, n), dtype=torch.float64, device=dev)
+    U_ext = torch.empty((Bn, S + N, m), dtype=torch.float64, device=dev)
+    rc = _lib.load().hop_onepass_extend_backward_f64(
+        sid, float(dt), _lib.ptr(X), _lib.ptr(U), _lib.ptr(uf), Bn, N, S, int(max_iter),
+        float(tol), float(damping), _lib.ptr(X_ext), _lib.ptr(U_ext), _lib.stream_handle(dev))
+    _lib.check(rc)
+    return X_ext, U_ext
+
+
+def onepass_pick(Vxx, Vx, V0, X_ext, x0, T_bar, T_min: int, T_max: int, S_left: int,
+                 S_right: int, *, wrap_idx=None, locality_mult: float = 5.0):
+    """Batched onepass_pick_T_singlepass (horizon_selection.py:215-282) with per-problem
+    T_bar [B]: Vxx [B, L, n, n], Vx [B, L, n], V0 [B, L] (riccati mode 1 on the extended
+    trajectory), X_ext [B, L, n], x0 [B, n] -> (T_star [B] int32, Jw [B, T_max], NaN where
+    not evaluated).  S_left, S_right as the reference passes them (its shrink loop hands in
+    an S_right below the arrays' offset)."""
+    torch = _torch()
+    X_ext = _dev(X_ext, "X_ext", torch.float64)
+    dev = X_ext.device
+    if X_ext.dim() != 3:
+        raise ValueError("X_ext must be [B, L, n]")
+    Bn, L, n = X_ext.shape
+    Vxx = _dev(Vxx, "Vxx", torch.float64, dev)
+    Vx = _dev(Vx, "Vx", torch.float64, dev)
+    V0 = _dev(V0, "V0", torch.float64, dev)
+    x0 = _dev(x0, "x0", torch.float64, dev)
+    if tuple(Vxx.shape) != (Bn, L, n, n) or tuple(Vx.shape) != (Bn, L, n) \
+            or tuple(V0.shape) != (Bn, L) or tuple(x0.shape) != (Bn, n):
+        raise ValueError(f"Vxx must be [B, L, {n}, {n}], Vx [B, L, {n}], V0 [B, L], x0 [B, {n}]")
+    T_min, T_max, S_left, S_right = int(T_min), int(T_max), int(S_left), int(S_right)
+    if not 1 <= T_min <= T_max:
+        raise ValueError("need 1 <= T_min <= T_max")
+    if not (0 <= S_left <= _lib.ONEPASS_MAX_WINDOW and 0 <= S_right <= _lib.ONEPASS_MAX_WINDOW):
+        raise ValueError(f"S_left, S_right must be in [0, {_lib.ONEPASS_MAX_WINDOW}]")
+    Tb = _int_vec(T_bar, Bn, dev, "T_bar")
+    T_star = torch.empty((Bn,), dtype=torch.int32, device=dev)
+    Jw = torch.empty((Bn, T_max), dtype=torch.float64, device=dev)
+    rc = _lib.load().hop_onepass_pick_f64(
+        _lib.ptr(Vxx), _lib.ptr(Vx), _lib.ptr(V0), _lib.ptr(X_ext), _lib.ptr(x0), _lib.ptr(Tb), Bn,
+        n, L, T_min, T_max, S_left, S_right, wrap_mask(wrap_idx, n), float(locality_mult),
+        _lib.ptr(T_star), _lib.ptr(Jw), _lib.stream_handle(dev))
+    _lib.check(rc)
+    return T_star, Jw
+
+
+@dataclass
+class OnepassRolloutResult:
+    X: "object"         # [B, N+1, n]  the best candidate (the nominal tail where none)
+    U: "object"         # [B, N, m]
+    J: "object"         # [B]  its true cost at T*, +inf where none
+    accepted: "object"  # [B] int32: alpha index, -1 none finite, -2 inactive
+    ok: "object"        # [B] bool: accepted >= 0 (the reference's fourth return value)
+
+
+def onepass_rollout(system, X_ext, U_ext, K, k, cost: CostParams, dt: float, T_bar, T_star,
+                    S_right: int, *, alphas=ONEPASS_ALPHAS, active=None) -> OnepassRolloutResult:
+    """Batched onepass_rollout (solver.py:365-442): X_ext [B, S+N+1, n], U_ext [B, S+N, m],
+    K [B, S+N, m, n], k [B, S+N, m] as riccati mode 1 returns them on the extended
+    trajectory; T_bar, T_star [B]; S_right = the arrays' offset; active [B] (None = all)."""
+    torch = _torch()
+    sid, n, m, X_ext, U_ext, dev = _traj_xu(_onepass_system(system), X_ext, U_ext)
+    Bn, S = U_ext.shape[0], int(S_right)
+    N = U_ext.shape[1] - S
+    if S < 0 or S > _lib.ONEPASS_MAX_WINDOW or N < 0:
+        raise ValueError(f"S_right must be in [0, {_lib.ONEPASS_MAX_WINDOW}] and at most the "
+                         "extended horizon")
+    K = _dev(K, "K", torch.float64, dev)
+    k = _dev(k, "k", torch.float64, dev)
+    if tuple(K.shape) != (Bn, S + N, m, n) or tuple(k.shape) != (Bn, S + N, m):
+        raise ValueError(f"K must be [B, S+N, {m}, {n}] and k [B, S+N, {m}]")
+    Tb = _int_vec(T_bar, Bn, dev, "T_bar")
+    Ts = _int_vec(T_star, Bn, dev, "T_star")
+    act = None if active is None else _int_vec(active, Bn, dev, "active")
+    al = [float(a) for a in alphas]
+    if not 1 <= len(al) <= 8:
+        raise ValueError("1..8 step sizes")
+    lib = _lib.load()
+    cargs, keep = cost.args(Bn, n, m, dev)
+    ws_bytes = int(lib.hop_onepass_rollout_workspace_bytes(sid, Bn, N, len(al)))
+    ws = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=dev)
+    Xn = torch.empty((Bn, N + 1, n), dtype=torch.float64, device=dev)
+    Un = torch.empty((Bn, N, m), dtype=torch.float64, device=dev)
+    J = torch.empty((Bn,), dtype=torch.float64, device=dev)
+    acc = torch.empty((Bn,), dtype=torch.int32, device=dev)
+    c_al = (_lib.C.c_double * len(al))(*al)
+    rc = lib.hop_onepass_rollout_f64(
+        sid, float(dt), _lib.ptr(X_ext), _lib.ptr(U_ext), *cargs, _lib.ptr(Tb), _lib.ptr(Ts),
+        _lib.ptr(act), _lib.ptr(K), _lib.ptr(k), c_al, len(al), Bn, N, S,
+        _lib.C.c_void_p(ws.data_ptr()), ws_bytes, _lib.ptr(Xn), _lib.ptr(Un), _lib.ptr(J),
+        _lib.ptr(acc), _lib.stream_handle(dev))
+    _lib.check(rc)
+    ws.record_stream(torch.cuda.current_stream(dev))
+    del keep
+    return OnepassRolloutResult(Xn, Un, J, acc, acc >= 0)

@@ -258,3 +258,29 @@ def bruteforce_all_Jt_backward_expansion(A_list, B_list, X, U, xg, u_ref, Q, R, 
     if (st.cpu().numpy() & (_lib.ST_FAIL | _lib.ST_NONFINITE)).any():
         raise np.linalg.LinAlgError("chol_solve failed: matrix not PD after jitter")
     return J[0].cpu().numpy()
+
+
+def onepass_pick_T_singlepass(Vxx, Vx, V0, X_ext, x0, T_bar: int, T_min: int, T_max: int,
+                              S_left: int, S_right: int, wrap_idx, *,
+                              locality_mult: float = 5.0) -> Tuple[int, np.ndarray]:
+    """horizon_selection.py:215-282 (GPU): (T*, Jw [T_max], NaN where not evaluated).
+    Vxx, Vx, V0: the lists value_expansions_and_gains_prefix returns (entries past their
+    end are never read: the reference would raise IndexError there, and so does this)."""
+    X_ext = np.asarray(X_ext, dtype=float)
+    L, n = X_ext.shape
+    T_bar, S_left, S_right = int(T_bar), int(S_left), int(S_right)
+    lo, hi = max(int(T_min), T_bar - S_left), min(int(T_max), T_bar + S_right)
+    idx = [T_bar - T + S_right for T in range(lo, hi + 1) if 0 <= T_bar - T + S_right < L]
+    if idx and max(idx) >= min(len(Vxx), len(Vx), len(V0)):
+        raise IndexError("list index out of range")
+    Vxx_a, Vx_a, V0_a = np.zeros((L, n, n)), np.zeros((L, n)), np.zeros(L)
+    for i in idx:
+        Vxx_a[i] = np.asarray(Vxx[i], dtype=float)
+        Vx_a[i] = np.asarray(Vx[i], dtype=float).reshape(-1)
+        V0_a[i] = float(V0[i])
+    T, Jw = engine.onepass_pick(_to_dev(Vxx_a)[None], _to_dev(Vx_a)[None], _to_dev(V0_a)[None],
+                                _to_dev(X_ext)[None],
+                                _to_dev(np.asarray(x0, dtype=float).reshape(1, -1)), [T_bar],
+                                int(T_min), int(T_max), S_left, S_right, wrap_idx=wrap_idx,
+                                locality_mult=locality_mult)
+    return int(T[0].item()), Jw[0].cpu().numpy()

@@ -83,3 +83,31 @@ def linearize_batch(F, X, U, *, central: bool = False, n_use=None, epsx: float =
     F = _check_F(F)
     return engine.linearize(_sys(F), X, U, F.dt, central=central, n_use=n_use, epsx=epsx,
                             epsu=epsu, relx=relx, relu=relu, want_fx=want_fx)
+
+
+def extend_nominal_backward(F, X, U, u_fill, *, S_back: int, preimage_method: str = "fixedpoint",
+                            max_iter: int = 6, tol: float = 1e-9, damping: float = 0.5):
+    """linearization.py:109-170 with the fixed-point preimage (linearization.py:41-71) on
+    the device: (X_ext [S_back + N + 1, n], U_ext [S_back + N, m]).  The Newton and copy
+    preimages have no kernel: NotImplementedError.  1 <= S_back <= 64 (S_back <= 0 returns
+    copies, as the reference does)."""
+    import torch
+    F = _check_F(F)
+    if engine.is_chain(F):
+        raise NotImplementedError("the negative-time prefix covers the five built-in systems")
+    pre = str(preimage_method).lower().strip()
+    if pre != "fixedpoint":  # the reference runs its fixed-point step for any other name too
+        raise NotImplementedError(f"preimage_method={pre!r}: only 'fixedpoint' runs on the device")
+    X = np.asarray(X, dtype=float)
+    U = np.asarray(U, dtype=float)
+    if U.ndim == 1:
+        U = U.reshape(-1, F.m)
+    if int(S_back) <= 0:
+        return X.copy(), U.copy()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=float), device=dev)  # noqa: E731
+    Xe, Ue = engine.extend_nominal_backward(F.system_id, t(X)[None], t(U)[None],
+                                            t(np.asarray(u_fill, dtype=float).reshape(-1)), F.dt,
+                                            int(S_back), max_iter=max_iter, tol=tol,
+                                            damping=damping)
+    return Xe[0].cpu().numpy(), Ue[0].cpu().numpy()

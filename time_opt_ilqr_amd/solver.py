@@ -10,9 +10,13 @@ and the accept / LM / stop-rule bookkeeping (hop_ilqr_accept_f64).  The host
 only sequences launches; it reads one flag per iteration (all problems done)
 to stop early.
 
+``method="bruteforce"`` swaps the select for the brute-force J curve;
+``method="onepass"`` (baseline2) is the loop of :mod:`time_opt_ilqr_amd.onepass`.
+
 The reference-shaped single-problem drop-ins (same names and arguments as
-solver.py) are ``rollout``, ``cost_timeopt_true``, ``forward_linesearch_fixedT``
-and ``ilqr_timeopt`` / ``ilqr_timeopt_ourmethod``.  F is a
+solver.py) are ``rollout``, ``cost_timeopt_true``, ``forward_linesearch_fixedT``,
+``nominal_cost_curve``, ``onepass_rollout`` and ``ilqr_timeopt`` /
+``ilqr_timeopt_ourmethod`` / ``ilqr_timeopt_baseline1`` / ``ilqr_timeopt_baseline2``.  F is a
 :class:`time_opt_ilqr_amd.systems.DeviceDynamics` (the make_* makers of
 :mod:`time_opt_ilqr_amd.systems` return one: everything on the device) or any
 Python callable F(x, u) -> x_next, and ``extra_stage_cost`` None, the point-mass
@@ -75,13 +79,18 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
                        wrap_idx: Optional[Sequence[int]] = None, use_central_diff: bool = True,
                        obstacles=None, alphas=ALPHAS, device=None,
                        stage_timers: bool = True, method: str = "propagator",
-                       extra_stage_cost=None) -> Dict[str, Any]:
-    """Batched ilqr_timeopt(method="propagator" | "bruteforce") (solver.py:449-765).
+                       extra_stage_cost=None, S_window: int = 20,
+                       onepass_preimage: str = "fixedpoint") -> Dict[str, Any]:
+    """Batched ilqr_timeopt(method="propagator" | "bruteforce" | "onepass")
+    (solver.py:449-765).
 
     The select step is the LFT sweep of the augmented system (propagator) or the
     brute-force J curve of T_max value-expansion sweeps (bruteforce, solver.py:293-358,
     one hop_bruteforce_jcurve launch, the wide entry's for n > 16); everything after it
-    is shared.
+    is shared.  method="onepass" (baseline2, with S_window and onepass_preimage) is the
+    loop of onepass.py: the five built-in device systems, 1 <= S_window <= 64, the
+    fixed-point preimage; its result also carries onepass_error, onepass_failed and
+    J_curve_valid.
 
     x0 [n] or [B, n] (torch or NumPy); U_init [B, N, m] or None (u_ref tiled);
     xg/u_ref/Q/R shared or per problem; Qf = as_terminal_weight(alpha) [n, n];
@@ -100,10 +109,19 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
     (c, cx, cxx) evaluated on the host the same way (host systems only; the device
     systems take the point-mass ``obstacles`` table).
     """
+    if method == "onepass":
+        from . import onepass
+        return onepass.solve_batch(system, x0, xg, u_ref, Q, R, Qf, w, N, T_min, T_max, dt=dt,
+                                   U_init=U_init, max_iter=max_iter, lm_init=lm_init,
+                                   wrap_idx=wrap_idx, use_central_diff=use_central_diff,
+                                   obstacles=obstacles, alphas=alphas, device=device,
+                                   stage_timers=stage_timers, S_window=S_window,
+                                   onepass_preimage=onepass_preimage,
+                                   extra_stage_cost=extra_stage_cost)
     torch = _torch()
     if method not in ("propagator", "bruteforce"):
         raise NotImplementedError(f"method={method!r}: the device outer loop implements "
-                                  "'propagator' and 'bruteforce'")
+                                  "'propagator', 'bruteforce' and 'onepass'")
     host = isinstance(system, host_dynamics.HostDynamics)
     if host:
         sid, n, m = None, int(system.n), int(system.m)
@@ -511,13 +529,20 @@ def ilqr_timeopt(F, x0, xg, u_ref, Q, R, alpha, w, N: int, T_min: int, T_max: in
                  lm_init: float = 1e-3, S_window: int = 20, wrap_idx: Optional[List[int]] = None,
                  use_central_diff: bool = True, extra_stage_cost=None,
                  onepass_preimage: str = "fixedpoint") -> Dict[str, Any]:
-    """solver.py:449-765 for one problem, method="propagator" or "bruteforce" (GPU end
-    to end).  S_window / onepass_preimage only matter for method="onepass" (not on
-    the device)."""
+    """solver.py:449-765 for one problem (GPU end to end).  S_window / onepass_preimage
+    only matter for method="onepass" (baseline2: the built-in device systems, the
+    obstacle table or no stage cost, the fixed-point preimage, 1 <= S_window <= 64)."""
+    if method == "onepass":
+        return _ilqr_timeopt_onepass(F, x0, xg, u_ref, Q, R, alpha, w, N, T_min, T_max,
+                                     U_init=U_init, max_iter=max_iter, lm_init=lm_init,
+                                     S_window=S_window, wrap_idx=wrap_idx,
+                                     use_central_diff=use_central_diff,
+                                     extra_stage_cost=extra_stage_cost,
+                                     onepass_preimage=onepass_preimage)
     if method not in ("propagator", "bruteforce"):
         raise NotImplementedError("the device outer loop implements method='propagator' "
-                                  "(the reference's 'ourmethod') and 'bruteforce' "
-                                  "('baseline1')")
+                                  "(the reference's 'ourmethod'), 'bruteforce' "
+                                  "('baseline1') and 'onepass' ('baseline2')")
     x0 = np.asarray(x0, dtype=float).reshape(1, -1)
     n = x0.shape[1]
     if _on_device(F) and _is_obstacle_cost(extra_stage_cost):
@@ -558,3 +583,90 @@ def ilqr_timeopt_ourmethod(*args, **kwargs):
 def ilqr_timeopt_baseline1(*args, **kwargs):
     """solver.py:775-776"""
     return ilqr_timeopt(*args, method="bruteforce", **kwargs)
+
+
+# ---------------------------------------------------------------------------
+# the one-pass window method (baseline2): reference-shaped drop-ins
+# ---------------------------------------------------------------------------
+
+def _onepass_system(F, extra_stage_cost, S_window=1, onepass_preimage="fixedpoint"):
+    """the scope of method="onepass" for a drop-in's F and stage cost"""
+    from . import onepass
+    if not _on_device(F):  # a Python callable
+        raise NotImplementedError("method='onepass' runs the built-in device systems "
+                                  "(systems.DeviceDynamics); Python callables are out of scope")
+    onepass.check_scope(F, S_window, onepass_preimage,
+                        None if _is_obstacle_cost(extra_stage_cost) else extra_stage_cost)
+    return _dyn(F)
+
+
+def _ilqr_timeopt_onepass(F, x0, xg, u_ref, Q, R, alpha, w, N, T_min, T_max, *, U_init, max_iter,
+                          lm_init, S_window, wrap_idx, use_central_diff, extra_stage_cost,
+                          onepass_preimage):
+    F = _onepass_system(F, extra_stage_cost, S_window, onepass_preimage)
+    x0 = np.asarray(x0, dtype=float).reshape(1, -1)
+    res = ilqr_timeopt_batch(F.system_id, x0, xg, u_ref, np.asarray(Q, dtype=float),
+                             np.atleast_2d(np.asarray(R, dtype=float)),
+                             as_terminal_weight(alpha, x0.shape[1]), float(w), N, T_min, T_max,
+                             dt=F.dt, obstacles=_obstacle_rows(extra_stage_cost), U_init=U_init,
+                             max_iter=max_iter, lm_init=lm_init, wrap_idx=wrap_idx,
+                             use_central_diff=use_central_diff, device=_dev(), method="onepass",
+                             S_window=S_window, onepass_preimage=onepass_preimage)
+    nh = int(res["n_hist"][0].item())
+    failed = int(res["onepass_failed"][0].item())
+    return {"X": res["X"][0].cpu().numpy(), "U": res["U"][0].cpu().numpy(),
+            "J_hist": [float(v) for v in res["J_hist"][0, :nh].cpu().numpy()],
+            "T_hist": [int(v) for v in res["T_hist"][0, :nh].cpu().numpy()],
+            "timers": res["timers"],
+            "J_curve": (res["J_curve"][0].cpu().numpy()
+                        if bool(res["J_curve_valid"][0].item()) else None),
+            "T_star": int(res["T_star"][0].item()),
+            "onepass_error": (f"value sweep failed (status {failed})" if failed else None)}
+
+
+def ilqr_timeopt_baseline2(*args, **kwargs):
+    """solver.py:778-779"""
+    return ilqr_timeopt(*args, method="onepass", **kwargs)
+
+
+def nominal_cost_curve(X, U, xg, u_ref, Q, R, alpha, w, T_min, T_max, wrap_idx=None,
+                       extra_stage_cost=None, *, system=None) -> np.ndarray:
+    """solver.py:108-149 (GPU).  ``system`` as in cost_timeopt_true."""
+    X = np.asarray(X, dtype=float)
+    U = np.asarray(U, dtype=float)
+    if U.ndim == 1:
+        U = U.reshape(-1, 1)
+    if not _is_obstacle_cost(extra_stage_cost):
+        raise NotImplementedError("a Python extra_stage_cost is out of scope on the device")
+    T_min, T_max = int(T_min), int(T_max)
+    if T_max > len(U) or T_max + 1 > len(X):
+        raise IndexError("index out of range")
+    sid = _system_for(system, X.shape[1], U.shape[1])
+    cost = _cost_params(X, xg, u_ref, Q, R, alpha, w, wrap_idx, extra_stage_cost)
+    J, _ = engine.nominal_cost_curve(sid, _t(X[:T_max + 1])[None], _t(U[:T_max])[None], cost,
+                                     T_min, T_max)
+    return J[0].cpu().numpy()
+
+
+def onepass_rollout(F, X_ext, U_ext, xg, u_ref, Q, R, alpha, w, K, k, *, T_bar, T_star, S_right,
+                    wrap_idx=None, extra_stage_cost=None, alphas=engine.ONEPASS_ALPHAS):
+    """solver.py:365-442 (GPU) -> (X_new, U_new, J_new, ok)."""
+    F = _onepass_system(F, extra_stage_cost)
+    X_ext = np.asarray(X_ext, dtype=float)
+    U_ext = np.asarray(U_ext, dtype=float)
+    if U_ext.ndim == 1:
+        U_ext = U_ext.reshape(-1, 1)
+    L, n, m = len(U_ext), X_ext.shape[1], U_ext.shape[1]
+    T_bar, T_star, S = int(T_bar), int(T_star), int(S_right)
+    lo, hi = T_bar - T_star + S, T_bar + S  # the gains the rollout reads: [lo, hi)
+    if T_star > 0 and (lo < 0 or hi > min(len(K), len(k), L)):
+        raise IndexError("list index out of range")
+    Kt, kt = np.zeros((L, m, n)), np.zeros((L, m))
+    for i in range(max(lo, 0), hi if T_star > 0 else 0):
+        Kt[i] = np.asarray(K[i], dtype=float).reshape(m, n)
+        kt[i] = np.asarray(k[i], dtype=float).reshape(-1)
+    cost = _cost_params(X_ext, xg, u_ref, Q, R, alpha, w, wrap_idx, extra_stage_cost)
+    r = engine.onepass_rollout(F.system_id, _t(X_ext)[None], _t(U_ext)[None], _t(Kt)[None],
+                               _t(kt)[None], cost, F.dt, [T_bar], [T_star], S, alphas=alphas)
+    return (r.X[0].cpu().numpy(), r.U[0].cpu().numpy(), float(r.J[0].item()),
+            int(r.accepted[0].item()) >= 0)
