@@ -163,6 +163,16 @@ ONEPASS_SIGNATURES = {
 }
 ONEPASS_MAX_WINDOW = 64  # include/hop_onepass.h HOP_ONEPASS_MAX_WINDOW
 
+# include/hop_testhooks.h (test support, not part of the product interface): the LDS fill
+# and its witness scan; bound beside the others
+TESTHOOK_SIGNATURES = {
+    # pattern groups_per_cu stream
+    "hop_test_lds_fill": (C.c_int, [C.c_uint64, _I32, _P]),
+    # pattern lds_bytes threads groups all_pattern stream
+    "hop_test_lds_scan": (C.c_int, [C.c_uint64, _I32, _I32, _I64, _P, _P]),
+}
+TEST_LDS_BYTES = 163840  # include/hop_testhooks.h HOP_TEST_LDS_BYTES
+
 
 class ChainParams(C.Structure):
     """hop_chain_params (include/hop_chain.h)."""
@@ -198,7 +208,8 @@ def load(path: str | None = None):
         for name, (res, args) in (list(SIGNATURES.items()) + list(WIDE_SIGNATURES.items())
                                   + list(WIDE_JCURVE_SIGNATURES.items())
                                   + list(CHAIN_SIGNATURES.items())
-                                  + list(ONEPASS_SIGNATURES.items())):
+                                  + list(ONEPASS_SIGNATURES.items())
+                                  + list(TESTHOOK_SIGNATURES.items())):
             if other and not hasattr(lib, name):
                 continue  # an older build loaded for an A/B (tools/ab_libs.py, HOP_LIB)
             fn = getattr(lib, name)

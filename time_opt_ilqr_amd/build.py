@@ -17,7 +17,7 @@ REPO = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libhop_amd.so")
 SOURCES = ["capi.hip", "augment.hip", "lft_sweep.hip", "lft_sweep_v2.hip", "lft_small.hip",
            "riccati.hip", "riccati_fast.hip", "linearize.hip", "forward.hip", "lft_wide.hip",
-           "riccati_wide.hip", "chain.hip", "onepass.hip"]
+           "riccati_wide.hip", "chain.hip", "onepass.hip", "lds_probe.hip"]
 # developer builds (HOP_DEV_BUILD=1 or --dev): the A/B schedules and stamped
 # instantiations, selected at run time by hop_set_options' variant number;
 # product builds compile none of them
@@ -57,7 +57,8 @@ def _digest():
     for name in SOURCES + DEV_SOURCES + HEADERS:
         with open(os.path.join(CSRC, name), "rb") as f:
             h.update(f.read())
-    for name in ("hop.h", "hop_wide.h", "hop_wide_jcurve.h", "hop_chain.h", "hop_onepass.h"):
+    for name in ("hop.h", "hop_wide.h", "hop_wide_jcurve.h", "hop_chain.h", "hop_onepass.h",
+                 "hop_testhooks.h"):
         with open(os.path.join(REPO, "include", name), "rb") as f:
             h.update(f.read())
     if ELIDE:  # the device code is what tools/nop_elide.py leaves of the compiler's

@@ -219,8 +219,10 @@ __device__ __forceinline__ void sym_spd_inverse(double (&r)[HR], const Ctx& w, i
   {
     double t[HR];
     get_t(w.L, t, w);
+    // for HR < 16 the lanes c >= 2 HR read rows this put has not written (what the
+    // kernel before left in LDS): only values from inside the block enter the registers
 #pragma unroll
-    for (int i = 0; i < HR; ++i) r[i] = 0.5 * (r[i] + t[i]);
+    for (int i = 0; i < HR; ++i) r[i] = live<HR>(w, i) ? 0.5 * (r[i] + t[i]) : 0.0;
   }
   double eps = 1e-9;
   int tries = 0;
@@ -251,7 +253,8 @@ __device__ __forceinline__ void sym_spd_inverse(double (&r)[HR], const Ctx& w, i
     double t[HR];
     get_t(w.L, t, w);
 #pragma unroll
-    for (int i = 0; i < HR; ++i) r[i] = 0.5 * (w.L[(w.h * HR + i) * kLd + w.c] + t[i]);
+    for (int i = 0; i < HR; ++i)
+      r[i] = live<HR>(w, i) ? 0.5 * (w.L[(w.h * HR + i) * kLd + w.c] + t[i]) : 0.0;
   }
   bool okl = true;
   if (lu) {
@@ -260,7 +263,8 @@ __device__ __forceinline__ void sym_spd_inverse(double (&r)[HR], const Ctx& w, i
 #pragma unroll
     for (int i = 0; i < HR; ++i) {
       const bool dg = live<HR>(w, i) && (w.h * HR + i == w.c);
-      a[i] = 0.5 * (w.L[(w.h * HR + i) * kLd + w.c] + a[i]) + (dg ? eps : 0.0);
+      a[i] = live<HR>(w, i)
+                 ? 0.5 * (w.L[(w.h * HR + i) * kLd + w.c] + a[i]) + (dg ? eps : 0.0) : 0.0;
     }
     wave_sync();
     put(w.L, a, w);

@@ -81,7 +81,10 @@ __device__ __forceinline__ double vec_sum(double x) {
 }
 __device__ __forceinline__ bool any_lane(bool p) { return __any(p) != 0; }
 
-// x <- 1/2 (x + x^T) through the left image
+// x <- 1/2 (x + x^T) through the left image.  put writes rows 0 .. 2 HR - 1 of the
+// image and get_t reads row c on every lane: for HR < 16 the lanes c >= 2 HR read rows
+// this put has not written (whatever the kernel before left in LDS), so only values
+// from inside the block enter the registers and the padding stays exact zeros.
 template <int HR>
 __device__ __forceinline__ void symmetrize(double (&x)[HR], const Ctx& w) {
   put(w.L, x, w);
@@ -90,7 +93,7 @@ __device__ __forceinline__ void symmetrize(double (&x)[HR], const Ctx& w) {
   get_t(w.L, t, w);
   wave_sync();
 #pragma unroll
-  for (int i = 0; i < HR; ++i) x[i] = 0.5 * (x[i] + t[i]);
+  for (int i = 0; i < HR; ++i) x[i] = live<HR>(w, i) ? 0.5 * (x[i] + t[i]) : 0.0;
 }
 
 // out (+)= X Y or X^T Y with explicit contraction count; x has XR rows per half, y YR,

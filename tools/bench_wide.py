@@ -16,6 +16,11 @@ Writes one JSON line per measurement:
     alternated round by round in this process; the curves are compared bit for bit
     before timing.  The row carries both ratios (loop over single launch) and the
     run-to-run spread of each side, (max - min) / median over the rounds.
+  * "wide_ab" (only with --only wide_ab --ab-lib OTHER.so): another build of the library
+    against this tree's on hop_riccati_wide_f64 mode 0 at n = 31 and n = 24 (m = 8), the J
+    curve at n = 31 and the sweep at s = 24, m = 4: the two alternated round by round in this
+    process (order flipped every round), outputs compared bit for bit; each row carries both
+    sides' rounds and their spread, (max - min) / median.
 --only measures the named kinds alone; the rewrite of --out replaces the rows of the
 kinds measured in this run and keeps every other row.
 Each line carries the FLOP and byte counts of bench.py's roofline (lft_flops /
@@ -65,6 +70,7 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--only", default="", help="comma-separated row kinds to measure")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "wide_sweep.jsonl"))
+    ap.add_argument("--ab-lib", default="", help="another build of libhop_amd.so (--only wide_ab)")
     args = ap.parse_args()
     import torch
     import bench
@@ -77,8 +83,10 @@ def main():
     rows = []
     kinds = ("wide_vs_generic", "wide_sweep", "wide_riccati", "wide_jcurve")
     only = tuple(k for k in args.only.split(",") if k) or kinds
-    if set(only) - set(kinds):
-        raise SystemExit(f"--only takes {', '.join(kinds)}")
+    if set(only) - set(kinds) - {"wide_ab"}:
+        raise SystemExit(f"--only takes {', '.join(kinds)}, wide_ab")
+    if "wide_ab" in only and not args.ab_lib:
+        raise SystemExit("--only wide_ab needs --ab-lib")
 
     def wide_call(A, Bm, Q, Ri, z0, QT, s, m):
         J = torch.empty((Bn, N), dtype=torch.float64, device=dev)
@@ -86,7 +94,7 @@ def main():
         r_bs = 0 if Ri.dim() == 2 else m * m
 
         def fn():
-            _lib.check(lib.hop_lft_sweep_wide_f64(
+            _lib.check(_lib.load().hop_lft_sweep_wide_f64(  # the library of the moment (wide_ab)
                 _lib.ptr(A), _lib.ptr(Bm), _lib.ptr(Q), _lib.ptr(Ri), r_bs, 0, 1, _lib.ptr(QT),
                 _lib.ptr(z0), 0, Bn, N, N, s, m, 8, 0, 0, _lib.ptr(J), _lib.ptr(st), None, None,
                 None, None, _lib.stream_handle(dev)))
@@ -199,6 +207,54 @@ def main():
                          frac_fp64_peak=fl * Bn / (large["jcurve_ms"] * 1e-3) / 1e12
                          / bench.PEAK_F64_TFLOPS))
         print(json.dumps(rows[-1]), flush=True)
+
+    # ---- another build of the library against this tree's, on the rows a change to the wide
+    # Riccati kernel or to hop_wide_device.hpp touches
+    if "wide_ab" in only:
+        base = _lib.load(args.ab_lib)
+        tree = _lib.load()
+
+        def spread(v):
+            return (max(v) - min(v)) / statistics.median(v)
+
+        def ab_row(name, fn, out_of, iters, **shape):
+            outs = []
+            for lb in (base, tree):  # warm-up and the outputs of each side
+                _lib._lib = lb
+                outs.append(out_of(fn()).clone())
+            torch.cuda.synchronize()
+            tb, tt = [], []
+            for rnd_ in range(args.rounds):  # alternate, order flipped every round
+                for which in ((0, 1) if rnd_ % 2 == 0 else (1, 0)):
+                    _lib._lib = base if which == 0 else tree
+                    (tb if which == 0 else tt).extend(_timed(fn, 1, iters))
+            _lib._lib = tree
+            mb, mt = statistics.median(tb), statistics.median(tt)
+            rows.append(dict(kind="wide_ab", workload=name, batch=Bn, N=N, **shape,
+                             base_lib=os.path.basename(args.ab_lib), base_ms=mb, base_ms_all=tb,
+                             tree_ms=mt, tree_ms_all=tt, ratio_tree_over_base=mt / mb,
+                             spread_base=spread(tb), spread_tree=spread(tt),
+                             bitwise_equal=bool(torch.equal(outs[0].nan_to_num(7.0),
+                                                            outs[1].nan_to_num(7.0)))))
+            print(json.dumps(rows[-1]), flush=True)
+
+        ab_row("wide_riccati_mode0", lambda: engine.riccati(A, Bm, X, U, xg, ur, Qc, Rc, Qf, T, 1e-3,
+                                                            mode=0), lambda r: r.K, args.iters,
+               n=n, m=m)
+        n2 = 24  # HR = 12, the instantiation whose padding lanes the symmetrisation read
+        A2, B2 = A[:, :, :n2, :n2].contiguous(), Bm[:, :, :n2].contiguous()
+        X2 = X[:, :, :n2].contiguous()
+        e2 = torch.eye(n2, dtype=torch.float64, device=dev)
+        ab_row("wide_riccati_mode0", lambda: engine.riccati(A2, B2, X2, U, xg[:n2], ur, e2, Rc,
+                                                            10.0 * e2, T, 1e-3, mode=0),
+               lambda r: r.K, args.iters, n=n2, m=m)
+        ab_row("wide_jcurve", lambda: engine.bruteforce_jcurve_wide(
+            A, Bm, X, U, xg, ur, Qc, Rc, Qf, N, lm_lambda=1e-6, w_stage=0.5), lambda r: r[0], 1,
+            n=n, m=m, t_max=N)
+        s2, m2 = 24, 4
+        sw = synth.device_batch(Bn, s2, m2, N, seed=5, device=dev)
+        fn, Jw, _ = wide_call(*sw, s2, m2)
+        ab_row("wide_sweep", fn, lambda _r: Jw, args.iters, s=s2, m=m2)
 
     # rows of other kinds (counter runs, the parent benchmark, the resource table) stay
     keep = []
