@@ -104,7 +104,7 @@ struct AugArgs {
 //   HOP_OPT_REFERENCE_ASSOC: no pair; the reference kernel alone, cond as the caller
 //                 gave it (0: every problem).
 // Which of this a path does is its CondPolicy (below).  Bits: who sets -> who reads.
-constexpr int kCondRerun = 1;        // rerun word; the fused bodies (device) -> LFT kernels
+constexpr int kCondRerun = 1;        // rerun word -> LFT kernels
 constexpr int kCondFlagAll = 2;      // first word, FORCE_HANDOVER -> conditioned kernels
 constexpr int kCondReason = 4;       // dev builds, NO_RERUN -> lft_sweep_v2.hip's cond kernels
 constexpr int kCondTriageOnly = 8;   // rerun word, NO_RERUN -> s = 13 fp64 rerun kernels
@@ -288,8 +288,6 @@ hipError_t dispatch_lft_v2(const LftArgs<double>& a, hipStream_t stream);
 //   kCondPolicyPlain (lft_small.hip, every shape, layout and dtype; fp32 s = 13, whose
 //     rerun goes through dispatch_lft<float>): first word 0 or kCondFlagAll; under
 //     NO_RERUN no second launch; rerun word kCondRerun.
-//   kCondPolicyFused (developer variants 60, 61): first word 0 or kCondFlagAll; no
-//     second launch from the host (the kernel recomputes its own hand-overs).
 // A developer variant that times the first kernel alone clears `rerun` in its copy.
 struct CondPolicy {
   bool reason;  // developer builds under NO_RERUN: the words carry kCondReason
@@ -301,7 +299,6 @@ struct CondPolicy {
 constexpr CondPolicy kCondPolicyS13 = {true, true, true, true, 0};
 constexpr CondPolicy kCondPolicyRowGroup = {true, false, false, true, kCondRerunOnly};
 constexpr CondPolicy kCondPolicyPlain = {false, false, false, true, 0};
-constexpr CondPolicy kCondPolicyFused = {false, false, false, false, 0};
 inline int cond_first_word(const CondPolicy& p) {
   return (opt(HOP_OPT_FORCE_HANDOVER) ? kCondFlagAll : 0) |
          ((p.reason && kDevBuild && opt(HOP_OPT_NO_RERUN)) ? kCondReason : 0);

@@ -27,21 +27,7 @@
 //
 // Schedules other than the defaults are compiled only in developer builds
 // (HOP_DEV, build.py --dev) and selected by hop_set_options' variant number:
-//   2  Select : compiler-scheduled pivots with lane-p selects (first v2)
-//   8  Chain  : offset form, short C++ pivot chain, pad-free DPP blocks
-//   10 Sched  : offset form, whole-sweep asm blocks
-//   12 SchedRow: Sched + X*Y products as one dependent DPP chain per output
-//      row (accumulator forwarded: 4.0 vs 4.9 cycles per FMA)
-//   14 SchedLdl: SchedRow + the query's Wt = (QT^-1 + Gbar)^-1 and its two
-//      products replaced by one LDL^T elimination that streams X0
-//   30 SchedLdlDma: SchedLdl with the step's LDS-DMA pieces from one asm block
-//      (the reference association; the rerun path of the conditioned kernels)
-//   20 / 32 stamped SchedLdl / SchedLdlDma (diagnostic, tools/stamps.py)
-//   40 (default) conditioned prefix SchedCondL + rerun; 41 without the rerun;
-//   42 its stamps (tools/stamps.py --cond); 43 SchedCond (no LDS reads inside
-//   the sweep blocks).  Trajectory form: 53 (default) closed-form stage
-//   inverses + rerun, 54 without; 40 / 41 Gauss-Jordan stage inverses; 24
-//   stamped SchedLdlTraj.
+// the table at dispatch_lft_v2 lists every one.
 #include <stdlib.h>
 
 #include "hop_device.hpp"
@@ -122,70 +108,36 @@ struct SchedCond : SchedLdlDma {
   static constexpr int AROW = 1;
   static constexpr int SCALE = 0;  // first attempts only: its own sweeps (rerun on doubt)
 };
-#ifndef HOP_COND_DMAI
-#define HOP_COND_DMAI 0  // A/B builds (tools/exp_build.py): the DMA pieces inside the update
-#endif
-constexpr bool kCondDmai = HOP_COND_DMAI != 0;
-#ifndef HOP_COND_SWEEP2
-#define HOP_COND_SWEEP2 0  // A/B: the s = 13 kernel's two sweeps as one interleaved block
-#endif
-constexpr bool kCondSweep2 = HOP_COND_SWEEP2 != 0;
-#ifndef HOP_COND_MFMA64
-#define HOP_COND_MFMA64 0  // A/B: the s = 13 fp64 predict on v_mfma_f64_16x16x4_f64
-#endif
-constexpr bool kCondMfma64 = HOP_COND_MFMA64 != 0;
 #ifndef HOP_SMALL_SWEEP2
 #define HOP_SMALL_SWEEP2 1  // small-s row groups: the two stage sweeps as one interleaved block
 #endif
 constexpr bool kSmallSweep2 = HOP_SMALL_SWEEP2 != 0;
-// + the QT image reads under the E sweep, the A/B reads under the X sweep
-#ifndef HOP_COND_WQ
-#define HOP_COND_WQ 1  // developer A/B builds (tools/exp_build.py): 0 = round 3's query
-#endif
+// + the QT image reads under the E sweep, the A/B reads under the X sweep and the
+// query by congruence (WQ: the X sweep stops one pivot short; see the query below):
+// the fp32-block kernel's schedule (halved symmetric sums), the base of the fp64 ones
 struct SchedCondL : SchedCond {
   static constexpr int LDSPIPE = 1;
-  static constexpr int WQ = HOP_COND_WQ;
+  static constexpr int WQ = 1;
 };
 template <class C>
 constexpr bool has_ldspipe() {
   if constexpr (requires { C::LDSPIPE; }) return C::LDSPIPE != 0;
   return false;
 }
-struct SchedCondLStamped : SchedCondL {
-  static constexpr int STAMP = 1;
-};
 // SYM2: the stage / terminal inverses of the UNHALVED symmetric sums (M + M^T:
 // inverse (2M)^-1 = M^-1 / 2, exact), consumed as fma(-2, NE, X) by the update and
-// the query with their diagonal offset at 2 (no 0.5 multiplies); the update's
-// Newton step on the reciprocal (CondLdl2); and the predict as one block whose
-// eps I rows come from LDS instead of lane selects (PredictEps)
-struct SchedCondL2 : SchedCondL {
-  static constexpr int SYM2 = 1, NEWT = 1, PEPS = 1;
+// the query with their diagonal offset at 2 (no 0.5 multiplies).  The base of the two
+// fp64 defaults below (no kernel of its own)
+struct SchedCondLSym : SchedCondL {
+  static constexpr int SYM2 = 1;
 };
-struct SchedCondL2Stamped : SchedCondL2 {
-  static constexpr int STAMP = 1;
-};
-// the three parts of SchedCondL2 alone (developer A/B)
-struct SchedCondLSym : SchedCondL {  // the default since round 3
-  static constexpr int SYM2 = 1, NEWT = 0, PEPS = 0;
-};
-// round 4: the query by congruence (the X sweep stops one pivot short; see the
-// query below): the default of SchedCondL and its descendants; WQ = 0 keeps the
-// round-3 query (developer variant 99, A/B)
 template <class C>
 constexpr bool has_wq() {
   if constexpr (requires { C::WQ; }) return C::WQ != 0;
   return false;
 }
-struct SchedCondLSymG : SchedCondLSym {
-  static constexpr int WQ = 0;
-};
-// the default without the periodic Sigma symmetrisation (developer variant 96, A/B)
-struct SchedCondLSymNS : SchedCondLSym {
-  static constexpr int NOSYM = 1;
-};
-// the symmetrisation after the step's DMA issue, through its own LDS scratch past the
-// four waves' areas (developer variant 93, A/B)
+// the default at one wave per SIMD: the periodic Sigma symmetrisation after the step's
+// DMA issue, through its own LDS scratch past the four waves' areas
 struct SchedCondLSymL : SchedCondLSym {
   static constexpr int SYMLATE = 1;
 };
@@ -193,11 +145,6 @@ template <class C>
 constexpr bool has_symlate() {
   if constexpr (requires { C::SYMLATE; }) return C::SYMLATE != 0;
   return false;
-}
-template <class C>
-constexpr bool has_sym_every() {
-  if constexpr (requires { C::NOSYM; }) return C::NOSYM == 0;
-  return true;
 }
 // the default at two waves per SIMD: packed images (Geo PACK), 2 workgroups per CU
 // (batches above one wave per SIMD)
@@ -209,50 +156,13 @@ constexpr bool has_pack() {
   if constexpr (requires { C::PACK; }) return C::PACK != 0;
   return false;
 }
-struct SchedCondLSymStamped : SchedCondLSym {
-  static constexpr int STAMP = 1;
-};
-// stamps of the round-4 default (the symmetrisation after the DMA issue)
+// stamps of the default (tools/stamps.py --cond)
 struct SchedCondLSymLStamped : SchedCondLSymL {
   static constexpr int STAMP = 1;
 };
-struct SchedCondLNewt : SchedCondL {
-  static constexpr int SYM2 = 0, NEWT = 1, PEPS = 0;
-};
-struct SchedCondLPeps : SchedCondL {
-  static constexpr int SYM2 = 0, NEWT = 0, PEPS = 1;
-};
-// SYM2 + the reciprocal Newton without the one-block predict (49 measured slower)
-struct SchedCondLSN : SchedCondL {
-  static constexpr int SYM2 = 1, NEWT = 1, PEPS = 0;
-};
-// DMA placement A/B: DSTAG 1 = odd waves issue the step's pieces after the update
-// (the CU's waves no longer burst together); 2 = Q/QT pieces after the E sweep
-// (their images are read by then), A/B after the X sweep
-struct SchedCondLStag1 : SchedCondL {
-  static constexpr int DSTAG = 1;
-};
-struct SchedCondLStag2 : SchedCondL {
-  static constexpr int DSTAG = 2;
-};
-template <class C>
-constexpr int dstag() {
-  if constexpr (requires { C::DSTAG; }) return C::DSTAG;
-  return 0;
-}
 template <class C>
 constexpr bool has_sym2() {
   if constexpr (requires { C::SYM2; }) return C::SYM2 != 0;
-  return false;
-}
-template <class C>
-constexpr bool has_newt() {
-  if constexpr (requires { C::NEWT; }) return C::NEWT != 0;
-  return false;
-}
-template <class C>
-constexpr bool has_peps() {
-  if constexpr (requires { C::PEPS; }) return C::PEPS != 0;
   return false;
 }
 
@@ -266,12 +176,15 @@ constexpr bool has_peps() {
 #ifndef HOP_SMALL_QPIPE
 #define HOP_SMALL_QPIPE 0  // small-s row groups: step k's query under step k+1's sweeps (A/B)
 #endif
+// (measured 8 % slower, DESIGN.md 3.9.  Still here because the product kernels' register
+// allocation moves when its compile-time-dead closures leave lft_cond_kernel: retiring
+// it is a change of the device code, to be made and measured on its own.)
 constexpr bool kSmallQPipe = HOP_SMALL_QPIPE != 0;
 #ifndef HOP_SMALL_STAMP
 #define HOP_SMALL_STAMP 0  // diagnostic builds: section stamps (tools/stamps_small.py)
 #endif
 struct SchedCondSmall : SchedCond {
-  static constexpr int SYM2 = 1, NEWT = 0, PEPS = 0, WQ = 1, SMALLS = 1;
+  static constexpr int SYM2 = 1, WQ = 1, SMALLS = 1;
   static constexpr int STAMP = HOP_SMALL_STAMP;
 };
 template <class C>
@@ -301,39 +214,6 @@ struct SchedCondTraj : SchedLdlDma {
   static constexpr int SCALE = 0;
   static constexpr int TRAJ = 1;
 };
-// fused hand-over: a wave whose problems the conditioned kernel flagged recomputes
-// them with the reference association (lft_v2_body) at the end of the same launch,
-// instead of a second (rerun) launch that every wave enters to read its status
-struct SchedCondLSymF : SchedCondLSym {
-  static constexpr int FUSE = 1;
-};
-struct SchedCondTrajF : SchedCondTraj {
-  static constexpr int FUSE = 1;
-};
-// lft_cond_cf_kernel with the round-3 query: the elimination of Sigma_eps + X_t with
-// X_t's 1/sigma ~ 1e9 rank-1 part formed (A/B, developer variant 97); the default
-// eliminates the congruent W^-T Sigma_eps W^-1 + diag(Pi, 1/sigma) instead
-struct SchedCondTrajG : SchedCondTraj {
-  static constexpr int GJQ = 1;
-};
-// without the periodic Sigma symmetrisation (developer A/B: 95; 94 = with the
-// round-3 query too, i.e. round 3's kernel)
-struct SchedCondTrajNS : SchedCondTraj {
-  static constexpr int NOSYM = 1;
-};
-struct SchedCondTrajGNS : SchedCondTrajG {
-  static constexpr int NOSYM = 1;
-};
-template <class C>
-constexpr bool has_gjq() {
-  if constexpr (requires { C::GJQ; }) return C::GJQ != 0;
-  return false;
-}
-template <class C>
-constexpr bool has_fuse() {
-  if constexpr (requires { C::FUSE; }) return C::FUSE != 0;
-  return false;
-}
 template <class C>
 constexpr bool has_traj() {
   if constexpr (requires { C::TRAJ; }) return C::TRAJ != 0;
@@ -1014,61 +894,6 @@ __device__ __forceinline__ void dma_step20(const unsigned (&vm)[6], const unsign
 }
 
 
-// The same 20 pieces in two groups (DSTAG 2): Q and QT (12) as soon as their
-// images are read, A and B (8) after the X sweep's reads
-template <int OQ, int OT>
-__device__ __forceinline__ void dma_stepQT(const unsigned (&vm)[6], __amdgpu_buffer_rsrc_t rQ,
-                                           __amdgpu_buffer_rsrc_t rT, unsigned wlds, unsigned soM) {
-  unsigned keep;
-#define HOP_P(R, V, OFF, SO)                                                  \
-  "s_add_u32 m0, %[w], " #OFF "\n\ts_nop 0\n\tbuffer_load_dwordx4 %[" #V "], %[" #R \
-  "], %[" #SO "] offen lds\n\t"
-  asm volatile(
-      HOP_VMNOP
-      ".p2align 3\n\t"  // every piece's 8-byte buffer_load at 0 mod 8 (code placement)
-      "s_waitcnt lgkmcnt(0)\n\t"
-      "s_mov_b32 %[keep], m0\n\t"
-      HOP_P(rq, v0, %[q0], sm) HOP_P(rq, v1, %[q1], sm) HOP_P(rq, v2, %[q2], sm)
-      HOP_P(rq, v3, %[q3], sm) HOP_P(rq, v4, %[q4], sm) HOP_P(rq, v5, %[q5], sm)
-      HOP_P(rt, v0, %[t0], sm) HOP_P(rt, v1, %[t1], sm) HOP_P(rt, v2, %[t2], sm)
-      HOP_P(rt, v3, %[t3], sm) HOP_P(rt, v4, %[t4], sm) HOP_P(rt, v5, %[t5], sm)
-      "s_mov_b32 m0, %[keep]"
-      : [keep] "=&s"(keep)
-      : [w] "s"(wlds), [sm] "s"(soM), [rq] "s"(rQ), [rt] "s"(rT), [v0] "v"(vm[0]),
-        [v1] "v"(vm[1]), [v2] "v"(vm[2]), [v3] "v"(vm[3]), [v4] "v"(vm[4]), [v5] "v"(vm[5]),
-        [q0] "i"(OQ), [q1] "i"(OQ + 1024), [q2] "i"(OQ + 2048), [q3] "i"(OQ + 3072),
-        [q4] "i"(OQ + 4096), [q5] "i"(OQ + 5120), [t0] "i"(OT), [t1] "i"(OT + 1024),
-        [t2] "i"(OT + 2048), [t3] "i"(OT + 3072), [t4] "i"(OT + 4096), [t5] "i"(OT + 5120)
-      : "memory", "scc");
-#undef HOP_P
-}
-template <int OA, int OB>
-__device__ __forceinline__ void dma_stepAB(const unsigned (&vm)[6], const unsigned (&vb)[2],
-                                           __amdgpu_buffer_rsrc_t rA, __amdgpu_buffer_rsrc_t rB,
-                                           unsigned wlds, unsigned soM, unsigned soB) {
-  unsigned keep;
-#define HOP_P(R, V, OFF, SO)                                                  \
-  "s_add_u32 m0, %[w], " #OFF "\n\ts_nop 0\n\tbuffer_load_dwordx4 %[" #V "], %[" #R \
-  "], %[" #SO "] offen lds\n\t"
-  asm volatile(
-      HOP_VMNOP
-      ".p2align 3\n\t"  // every piece's 8-byte buffer_load at 0 mod 8 (code placement)
-      "s_waitcnt lgkmcnt(0)\n\t"
-      "s_mov_b32 %[keep], m0\n\t"
-      HOP_P(ra, v0, %[a0], sm) HOP_P(ra, v1, %[a1], sm) HOP_P(ra, v2, %[a2], sm)
-      HOP_P(ra, v3, %[a3], sm) HOP_P(ra, v4, %[a4], sm) HOP_P(ra, v5, %[a5], sm)
-      HOP_P(rb, u0, %[b0], sb) HOP_P(rb, u1, %[b1], sb)
-      "s_mov_b32 m0, %[keep]"
-      : [keep] "=&s"(keep)
-      : [w] "s"(wlds), [sm] "s"(soM), [sb] "s"(soB), [ra] "s"(rA), [rb] "s"(rB),
-        [v0] "v"(vm[0]), [v1] "v"(vm[1]), [v2] "v"(vm[2]), [v3] "v"(vm[3]), [v4] "v"(vm[4]),
-        [v5] "v"(vm[5]), [u0] "v"(vb[0]), [u1] "v"(vb[1]), [a0] "i"(OA), [a1] "i"(OA + 1024),
-        [a2] "i"(OA + 2048), [a3] "i"(OA + 3072), [a4] "i"(OA + 4096), [a5] "i"(OA + 5120),
-        [b0] "i"(OB), [b1] "i"(OB + 1024)
-      : "memory", "scc");
-#undef HOP_P
-}
-
 // PACK (the conditioned kernel at two waves per SIMD, SchedCondLSymP): the images
 // packed back to back (the last DMA piece of each block type runs on the lanes that
 // carry data only, so nothing is written past an image) and the tile slot cut to the
@@ -1424,8 +1249,8 @@ __device__ __forceinline__ bool nonfinite_resolve(const LftArgs<double>& a, int 
 
 // The exact-size LFT sweep of one wave's 4 problems (the kernel below).  need: -1 =
 // a.cond's semantics (rerun launch: the problems whose status carries ST_RERUN);
-// 0 / 1 = this lane's problem is (not) recomputed -- the conditioned kernel's fused
-// hand-over passes its own flags here instead of a second launch.
+// 0 / 1 = this lane's problem is (not) recomputed -- the pipelined rerun's fallback
+// (lft_rerun_pipe_kernel) passes the flags left after its own triage.
 template <class C, int S, int MM>
 __device__ __forceinline__ void lft_v2_body(LftArgs<double> a, int need_in) {
   using G = Geo<S, MM>;
@@ -1451,7 +1276,7 @@ __device__ __forceinline__ void lft_v2_body(LftArgs<double> a, int need_in) {
   const long long wave_prob0 = ((long long)blockIdx.x * kWavesPerBlock + w) * kProbPerWave;
   const long long prob = wave_prob0 + g;
   bool valid = prob < a.batch;
-  if (need_in >= 0) {  // fused hand-over: the caller's flags
+  if (need_in >= 0) {  // the pipelined rerun's fallback: the caller's flags
     valid = valid && need_in != 0;
     if (!__any(valid)) return;
   } else if (a.cond & kCondRerun) {  // after SchedCond: only the problems it handed over
@@ -2744,8 +2569,7 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
                                    2 * kWavesPerBlock * G::WAVE_BYTES <= 160 * 1024),
                 "packed images: s = 13 fp64 blocks, two workgroups per CU");
   constexpr bool TRAJ = has_traj<C>();
-  static_assert(!F32 || (!TRAJ && dstag<C>() == 0 && !has_sym2<C>() && !has_peps<C>()),
-                "fp32 blocks: augmented form, halved sums");
+  static_assert(!F32 || (!TRAJ && !has_sym2<C>()), "fp32 blocks: augmented form, halved sums");
   constexpr int NN = G::NN;
   static_assert(S < kRowLanes, "m rides on lane S");
   static_assert(G::TILE_W >= 8 * S * S + 64, "zero area in the tile slot");
@@ -2762,28 +2586,13 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
   static_assert(!MF || (F32 && S == 13 && MM == 4), "MFMA predict: fp32 blocks, s = 13");
   // MFMA: the zero area grows to 2,880 B (a zero and a 1.0f for every problem's
   // image offset p * IMGM, p < 4) and the f32 staging region follows it
-  // MF64 (HOP_COND_MFMA64, A/B): the fp64 predict's two products on v_mfma_f64_16x16x4_f64,
-  // one problem per 16 x 16 tile; [Sigma' | m'] staged through the Q image and the result
-  // through the QT image (both read by then), so the step's DMA moves after the predict.
-  // Zero area: zeros at every p * 1360 (image offsets) and p * 1472 (staging offsets),
-  // a 1.0 at 1416 + p * 1360 (A~'s (13, 13), the m' pass-through), p < 4.
-  constexpr bool MF64 = kCondMfma64 && has_symlate<C>() && has_sym2<C>() && !has_newt<C>() &&
-                        !has_peps<C>() && !TRAJ && !F32 && !has_pack<C>() && S == 13 && MM == 4 &&
-                        dstag<C>() == 0;
-  constexpr int M6XP = 1472, M6ONE = 1416;  // staging stride per problem, 1.0 offset (bytes)
-  static_assert(!MF64 || (G::IMGM == 1360 && M6ONE + 3 * G::IMGM + 8 <= G::TILE_W &&
-                          4 * M6XP <= G::IMGM_W && 8 * (S * S + 8) <= M6ONE),
-                "fp64 MFMA staging: Q / QT image areas, ones past the sym zero area");
-  constexpr int ZB = MF ? 2880 : (MF64 ? 3 * M6XP + 8 : 8 * (S * S + 8));
+  constexpr int ZB = MF ? 2880 : 8 * (S * S + 8);
   constexpr int MFB = 2880, MFP = 1152;  // staging region offset, bytes per problem
   static_assert(!MF || (MFB + 4 * MFP <= G::TILE_W && 800 + 3 * G::IMGM + 4 <= ZB &&
                         G::IMGM == 688),
                 "MFMA staging in the tile slot");
 #pragma unroll 1
   for (int i = lane; i < ZB / 8; i += 64) zarea[i] = 0.0;
-  if constexpr (MF64) {
-    if (lane < 4) zarea[(M6ONE + lane * G::IMGM) / 8] = 1.0;
-  }
   if constexpr (MF) {
     float* mz = reinterpret_cast<float*>(wbase + G::OFF_T + MFB);
 #pragma unroll 1
@@ -2792,14 +2601,6 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
     // float index no other zero-area read uses (13 i and i, i < 13)
     if (lane < 4) reinterpret_cast<float*>(zarea)[200 + lane * (G::IMGM / 4)] = 1.0f;
   }
-  // SYM2: eps I rows for the predict, read as element 15 + I - c of a zero-padded
-  // vector holding eps at element 15 (after the zero area)
-  constexpr int EPSV = 192;  // doubles from the zero area's start
-  static_assert(!has_peps<C>() || G::TILE_W >= 8 * (EPSV + 32), "eps vector in the tile slot");
-  if constexpr (has_peps<C>()) {
-    if (lane < 32) zarea[EPSV + lane] = lane == 15 ? 1e-9 : 0.0;
-  }
-  const unsigned eps_addr = zaddr + 8u * (EPSV + 15 - c);
   constexpr double DOFF = has_sym2<C>() ? 1e-9 - 0.5 : 1e-9 - 1.0;  // image diagonal offset
   constexpr double KOFF = has_sym2<C>() ? 2.0 : 1.0;  // update / query diagonal offset
   // the congruence query (has_wq): the ldspipe schedules on augmented images only
@@ -2989,34 +2790,6 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
     }
   }
 
-  // MF64 operand addresses (problem p at an immediate offset: p * M6XP in the staging,
-  // p * IMGM in the A image; invalid lanes read the zero area at the same offsets):
-  //   f64 MFMA C/D map (cdna_hip_programming.md): lane (g, c) holds row g + 4 r, column c
-  //   of register r; A / B as the f32 16x16x4 form (A[c][k], B[k][c], k = lane group).
-  //   product 1 (T = [Sigma' | m'] A~^T), slice kk: lane (g, c) carries k = 4 g + kk:
-  //     A operand X[c][k] (staged [p][row][14]), B operand A~^T[k][c] = A[c][k] (+ the 1.0);
-  //   product 2 (A T), slice kk: k = g + 4 kk, so the B operand is register kk of T's
-  //     accumulator (row g + 4 kk, column c) and the A operand A[c][g + 4 kk];
-  //   the result (row g + 4 r, column c) goes to the QT image as [p][column][13].
-  unsigned m6_xw = 0, m6_xa[4] = {}, m6_aa[4] = {}, m6_ab[4] = {}, m6_dw = 0, m6_xr = 0;
-  if constexpr (MF64) {
-    const unsigned qb = lds_addr(imQ) - (unsigned)(g * G::IMGM);  // the wave's Q image area
-    const unsigned tb = lds_addr(imT) - (unsigned)(g * G::IMGM);
-    const unsigned ab = lds_addr(imA) - (unsigned)(g * G::IMGM);
-    m6_xw = qb + (unsigned)(g * M6XP) + 8u * c;
-    m6_dw = tb + 8u * (S * c + g);
-    m6_xr = c < S + 1 ? tb + (unsigned)(g * M6XP) + 8u * S * c : zaddr;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const int kx = 4 * g + kk;
-      m6_xa[kk] = (c < S && kx < S + 1) ? qb + 8u * ((S + 1) * c + kx) : zaddr;
-      const bool in = c < S && kx < S;
-      m6_ab[kk] = in ? ab + 8u * (S * c + kx) : (c == S && kx == S ? zaddr + M6ONE : zaddr);
-      const int k2 = g + 4 * kk;  // product 2's k (the accumulator's row map)
-      m6_aa[kk] = (c < S && k2 < S) ? ab + 8u * (S * c + k2) : zaddr;
-    }
-  }
-
   dma_step(0);
   double best = 0.0, jprev = 0.0;
   int tbest = 0;
@@ -3126,38 +2899,6 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
 #pragma unroll
       for (int q = 0; q < MM; ++q) brow[q] = (double)o2[2 * S + q];
       stamp(3);
-    } else if constexpr (has_ldspipe<C>() && !TRAJ && kCondSweep2 && WQ && has_sym2<C>() &&
-                         S == 13 && MM == 4 && dstag<C>() == 0) {
-      // Q's and QT's symmetric sums behind one LDS round trip, then the two independent
-      // sweeps as one interleaved block (each sweep's pivot chains hide behind the
-      // other's FMAs) with A_k's / B_k's reads underneath
-      const bool in = c < S;
-      const unsigned iq = lds_addr(imQ), it = lds_addr(imT);
-      const unsigned a4[4] = {in ? iq + 8u * c : zaddr, in ? iq + 8u * S * c : zaddr,
-                              in ? it + 8u * c : zaddr, in ? it + 8u * S * c : zaddr};
-      double qq[4 * S];
-      LdsSym2<S, S>::run(a4, qq);
-#pragma unroll
-      for (int i = 0; i < S; ++i) {
-        NE[i] = qq[i] + qq[S + i];
-        NX[i] = qq[2 * S + i] + qq[3 * S + i];
-      }
-      stamp(2);
-      double d1 = 1.0, d2 = 1.0;
-      double o2[2 * S + MM];
-      const unsigned ab[3] = {in ? lds_addr(imA) + 8u * S * c : zaddr, lds_addr(imA) + 8u * c,
-                              in ? lds_addr(imB) + 8u * MM * c : zaddr};
-      SweepQ2AB<S>::run(NE, d1, NX, d2, o2, ab);  // X: pivots 0 .. S-2 (the congruence query)
-      bad = bad || !pivots_ok(NE, d1) || !pivots_ok(NX, d2);
-      flag(!pivots_ok(NE, d1) || !pivots_ok(NX, d2), 1, k + 1);
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-        at[j] = o2[j];
-        if constexpr (has_arow<C>()) ar[j] = o2[S + j];
-      }
-#pragma unroll
-      for (int q = 0; q < MM; ++q) brow[q] = o2[2 * S + q];
-      stamp(3);
     } else if constexpr (has_ldspipe<C>() && !TRAJ) {
       // QT's sym reads ride under the E sweep, A_k / B_k's under the X sweep
       sym_from_z<C, S>(imQ, zaddr, c, NE);
@@ -3168,11 +2909,6 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
                               in ? lds_addr(imT) + 8u * S * c : zaddr};
       double d1 = 1.0, d2 = 1.0;
       SweepQSym<S>::run(NE, FOLD ? fmin : d1, o, aq);
-      if constexpr (dstag<C>() == 2) {  // the Q and QT images are read: refill them now
-        wave_sync();
-        if (k + 1 < N)
-          dma_stepQT<G::OFF_Q, G::OFF_QT>(voM, rQ, rT, wlds, (unsigned)((k + 1) * SS * ES));
-      }
 #pragma unroll
       for (int i = 0; i < S; ++i) NX[i] = has_sym2<C>() ? o[i] + o[S + i] : 0.5 * (o[i] + o[S + i]);
       double o2[2 * S + MM];
@@ -3275,39 +3011,25 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
     }
     }
     at[S] = e_s;
-    const bool dma_late = dstag<C>() == 1 && (w & 1);
-    // the step's DMA pieces spread through the update block instead of one burst
-    // before it (HOP_COND_DMAI, SchedCondLSymL only)
-    constexpr bool dmai = kCondDmai && has_symlate<C>() && has_sym2<C>() && !has_newt<C>() &&
-                          !TRAJ && !F32 && !has_pack<C>() && S == 13 && MM == 4;
-    if constexpr (dstag<C>() == 2) {
-      wave_sync();
-      if (k + 1 < N)
-        dma_stepAB<G::OFF_A, G::OFF_B>(voM, voB, rA, rB, wlds, (unsigned)((k + 1) * SS * ES),
-                                       (unsigned)((k + 1) * SM * ES));
-    } else {
-      // the step's images are consumed: the Q and A image areas are the symmetrisation
-      // scratch (the four problems' S x S doubles: 5,408 B, more than one fp32 image)
-      if constexpr (!TRAJ && has_sym_every<C>() && !has_symlate<C>()) {
-        static_assert(kProbPerWave * S * S * 8 <= G::OFF_QT, "scratch within the Q and A images");
-        if (sym_step(k))
-          sym_average<S>(reinterpret_cast<double (&)[S]>(X),
-                            reinterpret_cast<double*>(wbase + G::OFF_Q) + g * S * S, c);
-      }
+    // the step's images are consumed: the Q and A image areas are the symmetrisation
+    // scratch (the four problems' S x S doubles: 5,408 B, more than one fp32 image)
+    if constexpr (!TRAJ && !has_symlate<C>()) {
+      static_assert(kProbPerWave * S * S * 8 <= G::OFF_QT, "scratch within the Q and A images");
+      if (sym_step(k))
+        sym_average<S>(reinterpret_cast<double (&)[S]>(X),
+                          reinterpret_cast<double*>(wbase + G::OFF_Q) + g * S * S, c);
     }
-    if (dstag<C>() != 2 && !dma_late) {
-      wave_sync();
-      if (k + 1 < N && !dmai && !MF64) dma_step(k + 1);
-      if constexpr (has_symlate<C>()) {
-        static_assert(!TRAJ && !has_pack<C>(), "own scratch: the one-wave layout");
-        if (sym_step(k)) {
-          double* scr = reinterpret_cast<double*>(smem_raw + kWavesPerBlock * WB) +
-                        (w * kProbPerWave + g) * S * S;
-          if constexpr (kSymSplit)
-            sym_load_average<S>(reinterpret_cast<double (&)[S]>(X), scr, c);
-          else
-            sym_average<S>(reinterpret_cast<double (&)[S]>(X), scr, c);
-        }
+    wave_sync();
+    if (k + 1 < N) dma_step(k + 1);
+    if constexpr (has_symlate<C>()) {
+      static_assert(!TRAJ && !has_pack<C>(), "own scratch: the one-wave layout");
+      if (sym_step(k)) {
+        double* scr = reinterpret_cast<double*>(smem_raw + kWavesPerBlock * WB) +
+                      (w * kProbPerWave + g) * S * S;
+        if constexpr (kSymSplit)
+          sym_load_average<S>(reinterpret_cast<double (&)[S]>(X), scr, c);
+        else
+          sym_average<S>(reinterpret_cast<double (&)[S]>(X), scr, c);
       }
     }
     stamp(4);
@@ -3318,40 +3040,10 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
       for (int i = 0; i < S; ++i) {
         // Sigma_eps + E_k - I (offset form); SYM2: NE = -E_k/2 + I, so - 2I
         r[i] = has_sym2<C>() ? __builtin_fma(-2.0, NE[i], X[i]) : X[i] - NE[i];
-        if constexpr (has_peps<C>())  // an opaque copy: X keeps its loop registers
-          asm("v_mov_b64 %0, %1" : "=v"(Ht[i]) : "v"(X[i]));
-        else
-          Ht[i] = X[i];
+        Ht[i] = X[i];
       }
       double dmin = 1.0;
-      if constexpr (dmai) {  // the next step's pieces issued inside the update block
-        {
-          // the last step re-reads its own blocks (in L2 / MALL), so the update has
-          // one form (two copies of the block spilled 40 VGPRs)
-          const int kn = k + 1 < N ? k + 1 : k;
-          DmaStep20 q;
-#pragma unroll
-          for (int j = 0; j < 6; ++j) q.v[j] = voMl[j];
-          q.u[0] = voBl[0];
-          q.u[1] = voBl[1];
-          q.rq = rQ;
-          q.ra = rA;
-          q.rb = rB;
-          q.rt = rT;
-          q.so_m = (unsigned)(kn * SS * ES);
-          q.so_b = (unsigned)(kn * SM * ES);
-          q.m0[0] = wlds + G::OFF_Q;
-          q.m0[1] = wlds + G::OFF_Q + 4096;
-          q.m0[2] = wlds + G::OFF_A;
-          q.m0[3] = wlds + G::OFF_A + 4096;
-          q.m0[4] = wlds + G::OFF_B;
-          q.m0[5] = wlds + G::OFF_QT;
-          q.m0[6] = wlds + G::OFF_QT + 4096;
-          CondLdlO2R0D<S>::run(r, Ht, X, dmin, q);
-        }
-      } else if constexpr (has_sym2<C>() && has_newt<C>()) CondLdl2<S>::run(r, Ht, X, dmin);
-      else if constexpr (has_sym2<C>()) CondLdlO2R0<S>::run(r, Ht, X, FOLD ? fmin : dmin);
-      else if constexpr (has_newt<C>()) CondLdlO1R1<S>::run(r, Ht, X, dmin);
+      if constexpr (has_sym2<C>()) CondLdlO2R0<S>::run(r, Ht, X, FOLD ? fmin : dmin);
       else CondLdl<S>::run(r, Ht, X, dmin);
       const double x = bcast<S - 1>(r[S - 1]);
       if constexpr (FOLD) {
@@ -3360,10 +3052,6 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
         bad = bad || !(dmin > 0.0) || (x != x);
         flag(!(dmin > 0.0) || (x != x), 4, k + 1);
       }
-    }
-    if (dma_late) {  // DSTAG 1: the odd waves' pieces, half a step after the even waves'
-      wave_sync();
-      if (k + 1 < N) dma_step(k + 1);
     }
     stamp(5);
     // ---- predict: Sigma_{k+1} = A Sigma' A^T + B R^-1 B^T + eps I, m_{k+1} = A m'
@@ -3404,51 +3092,6 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
           X[I] = (double)*reinterpret_cast<const float*>(lds_ptr(ms_r + 4u * I)) +
                  sel_lane<I>(0.0, 1e-9);
         });
-      } else if constexpr (MF64) {
-        typedef double d4 __attribute__((ext_vector_type(4)));
-        if (c < S + 1) {  // stage [Sigma' | m'] rows: [p][row][14] doubles in the Q image
-#pragma unroll
-          for (int i = 0; i < S; ++i)
-            *reinterpret_cast<double*>(lds_ptr(m6_xw + 8u * (S + 1) * i)) = X[i];
-        }
-        wave_sync();
-        double xa[4][4], aa[4][4], bb[4][4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            xa[kk][q] = *reinterpret_cast<const double*>(lds_ptr(m6_xa[kk] + q * M6XP));
-            aa[kk][q] = *reinterpret_cast<const double*>(lds_ptr(m6_aa[kk] + q * G::IMGM));
-            bb[kk][q] = *reinterpret_cast<const double*>(lds_ptr(m6_ab[kk] + q * G::IMGM));
-          }
-        d4 D1[4], D2[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) D1[q] = D2[q] = (d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            D1[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[kk][q], bb[kk][q], D1[q], 0, 0, 0);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            D2[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(aa[kk][q], D1[q][kk], D2[q], 0, 0, 0);
-        wave_sync();  // the staging reads are done: the QT image takes the result
-        if (c < S + 1) {  // rows g + 4 r < S of column c, as [p][column][13]
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (g + 4 * r < S)
-                *reinterpret_cast<double*>(lds_ptr(m6_dw + q * M6XP + 32u * r)) = D2[q][r];
-        }
-        wave_sync();
-        static_for<S>([&](auto I) {
-          X[I] = *reinterpret_cast<const double*>(lds_ptr(m6_xr + 8u * I)) + sel_lane<I>(0.0, 1e-9);
-        });
-      } else if constexpr (has_peps<C>()) {
-        PredictEps<S>::run(Xs, Tm, at, ar, eps_addr);  // eps I + A [Sigma' | m'] A~^T
       } else {
       // T = [Sigma' | m'] A~^T; A~^T's row S is e_S, so its term is X masked to lane S
 #pragma unroll
@@ -3476,10 +3119,6 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
                                (w * kProbPerWave + g) * S * S,
                        c);
       }
-    }
-    if constexpr (MF64) {  // the Q / QT / A images are read: the next step's pieces
-      wave_sync();
-      if (k + 1 < N) dma_step(k + 1);
     }
     stamp(6);
     if constexpr (QPIPE) {  // the query runs in the next step (or after the loop)
@@ -3599,18 +3238,7 @@ __global__ __launch_bounds__(256, has_pack<C>() ? 2 : 1) void lft_cond_kernel(Lf
       a.j_star[prob] = (T)best;
     }
   }
-  if constexpr (has_fuse<C>()) {
-    static_assert(!F32, "fused hand-over: fp64 blocks");
-    const bool hand = valid && bad;
-    if (__any(hand)) {  // wave-uniform; the rerun body uses this wave's LDS only
-      LftArgs<double> r = a;
-      r.cond = kCondRerun;
-      using RC = std::conditional_t<TRAJ, SchedLdlTraj, SchedLdlDma>;
-      lft_v2_body<RC, S, MM>(r, hand ? 1 : 0);
-    }
-  }
 }
-
 
 
 // ===========================================================================
@@ -3822,12 +3450,12 @@ __global__ __launch_bounds__(256, 1) void lft_cond_cf_kernel(LftArgs<double> a) 
     at[S] = e_s;
     // the periodic symmetrisation (split: the rows were stored after the last predict);
     // its reads share their round trip with e_{k+1}'s below (X is first needed after)
-    constexpr bool SYMI = kSymSplit && has_sym_every<C>() && S == 13;
+    constexpr bool SYMI = kSymSplit && S == 13;
     double ysym[S];
     const bool sy = sym_step(k);
     if constexpr (SYMI) {
       if (sy) sym_issue13(csym, c, reinterpret_cast<double (&)[13]>(ysym));
-    } else if constexpr (kSymSplit && has_sym_every<C>()) {
+    } else if constexpr (kSymSplit) {
       if (sy) sym_load_average<S>(reinterpret_cast<double (&)[S]>(X), csym, c);
     }
     // ---- e_{k+1}: the terminal block of horizon k+1 and the next stage block
@@ -3863,7 +3491,7 @@ __global__ __launch_bounds__(256, 1) void lft_cond_cf_kernel(LftArgs<double> a) 
       LaneB<S>::fma(r, wp, vp);  // + w' v'^T
     }
     // ---- update: condition the prefix on stage k's cost
-    if (!kSymSplit && has_sym_every<C>() && sym_step(k))
+    if (!kSymSplit && sym_step(k))
       sym_average<S>(reinterpret_cast<double (&)[S]>(X), csym, c);
     {
       double Ht[S];
@@ -3887,7 +3515,7 @@ __global__ __launch_bounds__(256, 1) void lft_cond_cf_kernel(LftArgs<double> a) 
       zero(y);
       acc_xy<false, double, MM, MM>(y, rinv, brow);
       acc_xty<false, double, S, MM>(Xs, brow, y);  // + B R^-1 B^T
-      if constexpr (kSymSplit && has_sym_every<C>()) {
+      if constexpr (kSymSplit) {
         if (sym_store_step(k, N)) sym_store<S>(Xs, csym, c);
       }
     }
@@ -3903,45 +3531,29 @@ __global__ __launch_bounds__(256, 1) void lft_cond_cf_kernel(LftArgs<double> a) 
       const double sig = (t.rho_reg + eps) + eps * eu;
       bad = bad || !(sig > 0.0);
       flag(!(sig > 0.0), 8, k + 1);
+      // X_t = W^T D W with D = diag(Pi, 1/sigma), W = [[I, 0], [-u^T, 1]] (u here the
+      // first NN lanes of u), so m^T (Sigma_eps + X_t)^-1 m = m~^T (Sigma~ + D)^-1 m~
+      // with Sigma~ = W^-T Sigma_eps W^-1, m~ = W^-T m, W^-1 = I + e_NN [u; 0]^T.  The
+      // 1/sigma ~ 1e9 of the terminal block then sits alone on the last diagonal
+      // entry: no pivot cancels it (eliminating Sigma_eps + X_t itself, round 3's query,
+      // lost 1e-7 .. 1e-5 of q on real quadrotor linearisations and handed problems
+      // the reference solves cleanly to the rerun; this form holds ~1e-16, measured
+      // against exact rational arithmetic)
+      // Pi_ext has a zero last row and column: W^-T Pi_ext W^-1 = Pi_ext, so it is
+      // added before the congruence
       double rq[S];
-      if constexpr (has_gjq<C>()) {
+      const double ub = in ? e1 - eps * z : 0.0;
 #pragma unroll
-        for (int i = 0; i < NN; ++i) rq[i] = X[i] + Pi[i];
-        rq[NN] = X[NN];
-      }
-      double q;
-      if constexpr (has_gjq<C>()) {  // round 3: eliminate Sigma_eps + X_t itself
-        const double wq = u * recip_nr(sig);
-        LaneB<S>::fma(rq, wq, u);
-        double acc = 0.0, dmin = 1.0;
-        ElimQ<S>::run(rq, acc, dmin, 0.0);
-        q = bcast<S>(acc);
-        bad = bad || !(dmin > 0.0) || (q != q);
-        flag(!(dmin > 0.0) || (q != q), 16, k + 1);
-      } else {
-        // X_t = W^T D W with D = diag(Pi, 1/sigma), W = [[I, 0], [-u^T, 1]] (u here the
-        // first NN lanes of u), so m^T (Sigma_eps + X_t)^-1 m = m~^T (Sigma~ + D)^-1 m~
-        // with Sigma~ = W^-T Sigma_eps W^-1, m~ = W^-T m, W^-1 = I + e_NN [u; 0]^T.  The
-        // 1/sigma ~ 1e9 of the terminal block then sits alone on the last diagonal
-        // entry: no pivot cancels it (the round-3 form, eliminating Sigma_eps + X_t,
-        // lost 1e-7 .. 1e-5 of q on real quadrotor linearisations and handed problems
-        // the reference solves cleanly to the rerun; this form holds ~1e-16, measured
-        // against exact rational arithmetic)
-        // Pi_ext has a zero last row and column: W^-T Pi_ext W^-1 = Pi_ext, so it is
-        // added before the congruence
-        const double ub = in ? e1 - eps * z : 0.0;
-#pragma unroll
-        for (int i = 0; i < NN; ++i) rq[i] = X[i] + Pi[i];
-        rq[NN] = X[NN];
-        RowB<S>::template sweep<NN>(rq, ub);  // (.) W^-1: row i += (.)_i,NN [u; 0]
-        LaneB<NN>::fma(reinterpret_cast<double (&)[NN]>(rq), ub, rq[NN]);  // W^-T (.): + u_i row NN
-        rq[NN] = __builtin_fma(e_nn, recip_nr(sig), rq[NN]);  // D's 1/sigma
-        double acc = 0.0, dmin = 1.0;
-        ElimQ<S>::run(rq, acc, dmin, 0.0);
-        q = bcast<S>(acc);
-        bad = bad || !(dmin > 0.0) || (q != q);
-        flag(!(dmin > 0.0) || (q != q), 16, k + 1);
-      }
+      for (int i = 0; i < NN; ++i) rq[i] = X[i] + Pi[i];
+      rq[NN] = X[NN];
+      RowB<S>::template sweep<NN>(rq, ub);  // (.) W^-1: row i += (.)_i,NN [u; 0]
+      LaneB<NN>::fma(reinterpret_cast<double (&)[NN]>(rq), ub, rq[NN]);  // W^-T (.): + u_i row NN
+      rq[NN] = __builtin_fma(e_nn, recip_nr(sig), rq[NN]);  // D's 1/sigma
+      double acc = 0.0, dmin = 1.0;
+      ElimQ<S>::run(rq, acc, dmin, 0.0);
+      const double q = bcast<S>(acc);
+      bad = bad || !(dmin > 0.0) || (q != q);
+      flag(!(dmin > 0.0) || (q != q), 16, k + 1);
       const double gam = bcast<S>(X[S]);
       jk = 0.5 * (q - gam);
     }
@@ -3975,14 +3587,6 @@ __global__ __launch_bounds__(256, 1) void lft_cond_cf_kernel(LftArgs<double> a) 
     if (fuse_argmin && a.t_star != nullptr) {
       a.t_star[prob] = tbest;
       a.j_star[prob] = best;
-    }
-  }
-  if constexpr (has_fuse<C>()) {  // the fused hand-over (see SchedCondTrajF)
-    const bool hand = valid && bad;
-    if (__any(hand)) {
-      LftArgs<double> r = a;
-      r.cond = kCondRerun;
-      lft_v2_body<SchedLdlTraj, S, MM>(r, hand ? 1 : 0);
     }
   }
 }
@@ -4031,8 +3635,51 @@ hipError_t dispatch_cond_small(const LftArgs<double>& a, hipStream_t stream) {
 // Product builds: the conditioned-prefix kernel + the rerun launch of the
 // reference association for the problems it flagged (HOP_OPT_REFERENCE_ASSOC:
 // the reference association alone; HOP_OPT_FORCE_HANDOVER: every problem handed
-// over).  Developer builds (HOP_DEV) add the A/B schedules of DESIGN.md 3.2 by
-// number (hop_set_options variant).
+// over).  Developer builds (HOP_DEV) add the schedules below by number
+// (hop_set_options variant).  Every number this file answers to:
+//
+//   s = 13, m = 4, fp64 augmented blocks (dispatch_lft_v2)
+//   no. | first launch / rerun launch            | what it is for                      | selected by
+//   ----+----------------------------------------+-------------------------------------+------------
+//   0,  | lft_cond_kernel<SchedCondLSymL> (above | the product default                 | everything
+//   40  | one wave per SIMD: <SchedCondLSymP>) / |                                     |
+//       | lft_rerun_pipe_kernel<SchedLdlDma>     |                                     |
+//   2   | lft_sweep_v2_kernel<Select>            | ancestry: lane-p select pivots      | test_lft_fast_path_
+//   8   | lft_sweep_v2_kernel<Chain>             | ancestry: offset form, C++ chain    |  matches_generic_kernel
+//   10  | lft_sweep_v2_kernel<Sched>             | ancestry: whole-sweep asm blocks    |  (test_gpu_parity.py),
+//   12  | lft_sweep_v2_kernel<SchedRow>          | ancestry: row-chain X*Y products    |  tools/ab_bench.py
+//   14  | lft_sweep_v2_kernel<SchedLdl>          | ancestry: LDL^T query               |
+//   30  | lft_sweep_v2_kernel<SchedLdlDma>       | the reference association (product: | the same test;
+//       |                                        | HOP_OPT_REFERENCE_ASSOC)            |  test_gpu_rerun.py
+//   20  | lft_sweep_v2_kernel<SchedStamped>      | section stamps of 14                | tools/stamps.py
+//   32  | lft_sweep_v2_kernel<SchedLdlDmaStamped>| section stamps of 30                | tools/stamps.py
+//   41  | the default's first launch alone       | timing without the rerun launch     | tools/ab_bench.py
+//   42  | lft_cond_kernel<SchedCondLSymLStamped> | section stamps of the default (also | tools/stamps.py --cond
+//       |                                        | HOP_OPT_STAMPS)                     |
+//   91  | the default, <SchedCondLSymP> forced   | packed layout at any batch          | tools/ab_bench.py
+//   92  | the default, <SchedCondLSymL> forced   | one-wave layout at any batch        | tools/ab_bench.py
+//
+//   s = 13, m = 4, fp64 trajectory form (dispatch_lft_v2, a.traj)
+//   0   | lft_cond_cf_kernel<SchedCondTraj> /    | the product default ("53" in        | everything
+//       | lft_rerun_pipe_kernel<SchedLdlTraj>    | DESIGN.md: closed-form inverses)    |
+//   54  | lft_cond_cf_kernel<SchedCondTraj>      | the default without the rerun       | test_gpu_traj.py
+//   40  | lft_cond_kernel<SchedCondTraj> /       | Gauss-Jordan stage inverses         | test_gpu_traj.py,
+//       | lft_sweep_v2_kernel<SchedLdlTraj>      |                                     |  tools/ab_traj.py
+//   41  | lft_cond_kernel<SchedCondTraj>         | 40 without the rerun                | test_gpu_traj.py
+//   24  | lft_sweep_v2_kernel<SchedLdlTrajStamped>| section stamps (also HOP_OPT_STAMPS)| tools/stamps.py --traj
+//
+//   s <= 5 fp64 row groups (dispatch_cond_small)
+//   80  | none: lft_small.hip's lane kernel      | A/B of the row-group kernel         | tools/ab_bench.py --s
+//
+//   s = 13, m = 4, fp32 blocks (dispatch_lft_v2_f32)
+//   0,  | lft_cond_kernel<SchedCondL, float> /   | the product default                 | everything
+//   40  | dispatch_lft<float>                    |                                     |
+//   41  | the default's first launch alone       | timing without the rerun            | tools/ab_bench.py
+//   56  | lft_cond_kernel<SchedCondMfma, float>  | the predict on the f32 matrix cores | test_gpu_configs.py,
+//   57  | 56 without the rerun                   |                                     |  tools/mfma_pmc.py
+//
+// Variant numbers are per file: riccati_fast.hip and forward.hip give their own
+// meanings to numbers this file once used (90, 93, 95 and 96).
 hipError_t dispatch_lft_v2(const LftArgs<double>& a, hipStream_t stream) {
   if (a.dbg_efg || a.dbg_pre || a.r_kstride != 0 || !a.r_is_inv) return hipErrorNotSupported;
   const long long blocks = (a.batch + kProbPerBlock - 1) / kProbPerBlock;
@@ -4070,24 +3717,11 @@ hipError_t dispatch_lft_v2(const LftArgs<double>& a, hipStream_t stream) {
     if (variant == 54)  // closed-form stage inverses without the rerun launch
       return cond_rerun(v2::lft_cond_cf_kernel<v2::SchedCondTraj, 13, 4>,
                         v2::lft_sweep_v2_kernel<v2::SchedLdlTraj, 13, 4>, bytes, false);
-    if (variant == 95)
-      return cond_rerun(v2::lft_cond_cf_kernel<v2::SchedCondTrajNS, 13, 4>,
-                        v2::lft_sweep_v2_kernel<v2::SchedLdlTraj, 13, 4>, bytes, true);
-    if (variant == 94)
-      return cond_rerun(v2::lft_cond_cf_kernel<v2::SchedCondTrajGNS, 13, 4>,
-                        v2::lft_sweep_v2_kernel<v2::SchedLdlTraj, 13, 4>, bytes, true);
-    if (variant == 97 || variant == 98)  // the round-3 query (+ rerun unless 98)
-      return cond_rerun(v2::lft_cond_cf_kernel<v2::SchedCondTrajG, 13, 4>,
-                        v2::lft_sweep_v2_kernel<v2::SchedLdlTraj, 13, 4>, bytes, variant == 97);
     if (variant == 40 || variant == 41)  // Gauss-Jordan stage inverses (+ rerun unless 41)
       return cond_rerun(v2::lft_cond_kernel<v2::SchedCondTraj, 13, 4>,
                         v2::lft_sweep_v2_kernel<v2::SchedLdlTraj, 13, 4>, bytes, variant == 40);
     if (variant == 24 || opt(HOP_OPT_STAMPS))  // section stamps (tools/stamps.py --traj)
       return launch(v2::lft_sweep_v2_kernel<v2::SchedLdlTrajStamped, 13, 4>, bytes, a);
-    if (variant == 61) {  // the fused hand-over (measured slower)
-      return launch(v2::lft_cond_cf_kernel<v2::SchedCondTrajF, 13, 4>, bytes,
-                    with_cond(a, cond_first_word(kCondPolicyFused)));
-    }
 #endif
     // default: closed-form stage inverses, then the pipelined rerun
     {
@@ -4111,55 +3745,11 @@ hipError_t dispatch_lft_v2(const LftArgs<double>& a, hipStream_t stream) {
     return launch(v2::lft_sweep_v2_kernel<v2::SchedLdlDma, 13, 4>, bytes, a);
 #ifdef HOP_DEV
   switch (variant) {
-    case 93:  // the default with round 4's one-wave LFT rerun launch (A/B of the pipeline)
-      return cond_rerun(v2::lft_cond_kernel<v2::SchedCondLSymL, 13, 4>,
-                        v2::lft_sweep_v2_kernel<v2::SchedLdlDma, 13, 4>, bytes_symlate, true);
-    case 96:  // the default without the periodic symmetrisation + rerun
-      return cond_rerun(v2::lft_cond_kernel<v2::SchedCondLSymNS, 13, 4>,
-                        v2::lft_sweep_v2_kernel<v2::SchedLdlDma, 13, 4>, bytes, true);
-    case 99:  // the round-3 query (the full X sweep, Sigma_eps + X_t eliminated) + rerun
-      return cond_rerun(v2::lft_cond_kernel<v2::SchedCondLSymG, 13, 4>,
-                        v2::lft_sweep_v2_kernel<v2::SchedLdlDma, 13, 4>, bytes, true);
     case 42:  // stamps of the default (tools/stamps.py --cond), no rerun
       return launch(v2::lft_cond_kernel<v2::SchedCondLSymLStamped, 13, 4>, bytes_symlate, a);
-    case 59:  // stamps of the round-2 default (halved sums), no rerun
-      return launch(v2::lft_cond_kernel<v2::SchedCondLStamped, 13, 4>, bytes, a);
-    case 43:  // image reads not overlapped with the sweeps, no rerun
-      return launch(v2::lft_cond_kernel<v2::SchedCond, 13, 4>, bytes, a);
-    case 44:  // SYM2 conditioned kernel + rerun
-      return cond_rerun(v2::lft_cond_kernel<v2::SchedCondL2, 13, 4>,
-                        v2::lft_sweep_v2_kernel<v2::SchedLdlDma, 13, 4>, bytes, true);
-    case 45:  // SYM2 without the rerun launch
-      return cond_rerun(v2::lft_cond_kernel<v2::SchedCondL2, 13, 4>,
-                        v2::lft_sweep_v2_kernel<v2::SchedLdlDma, 13, 4>, bytes, false);
-    case 46:  // SYM2 stamps, no rerun
-      return launch(v2::lft_cond_kernel<v2::SchedCondL2Stamped, 13, 4>, bytes, a);
-    case 50:  // DMA: odd waves after the update, no rerun
-      return launch(v2::lft_cond_kernel<v2::SchedCondLStag1, 13, 4>, bytes, a);
-    case 51:  // DMA: Q/QT after the E sweep, A/B after the X sweep, no rerun
-      return launch(v2::lft_cond_kernel<v2::SchedCondLStag2, 13, 4>, bytes, a);
-    case 47:  // the unhalved sums alone (the default's kernel), no rerun
-      return launch(v2::lft_cond_kernel<v2::SchedCondLSym, 13, 4>, bytes, a);
-    case 48:  // the update's Newton on the reciprocal alone, no rerun
-      return launch(v2::lft_cond_kernel<v2::SchedCondLNewt, 13, 4>, bytes, a);
-    case 49:  // the one-block predict with LDS eps rows alone, no rerun
-      return launch(v2::lft_cond_kernel<v2::SchedCondLPeps, 13, 4>, bytes, a);
-    case 52:  // the unhalved sums + the reciprocal Newton (47 + 48), no rerun
-      return launch(v2::lft_cond_kernel<v2::SchedCondLSN, 13, 4>, bytes, a);
     case 41:  // the default's conditioned kernel without the rerun launch (A/B timing)
       return cond_rerun(v2::lft_cond_kernel<v2::SchedCondLSymL, 13, 4>,
                         v2::lft_sweep_v2_kernel<v2::SchedLdlDma, 13, 4>, bytes_symlate, false);
-    case 90:  // round 4's first placement: the symmetrisation before the DMA issue, + rerun
-      return cond_rerun(v2::lft_cond_kernel<v2::SchedCondLSym, 13, 4>,
-                        v2::lft_sweep_v2_kernel<v2::SchedLdlDma, 13, 4>, bytes, true);
-    case 58:  // round-2 default (halved symmetric sums) without the rerun launch
-      return launch(v2::lft_cond_kernel<v2::SchedCondL, 13, 4>, bytes, a);
-    case 60: {  // fused hand-over: flagged problems recomputed at the end of the same
-                // launch (lft_v2_body); the kernel then carries the LFT body's scratch and
-                // measured 0.7-2 % slower than the default's second launch
-      return launch(v2::lft_cond_kernel<v2::SchedCondLSymF, 13, 4>, bytes,
-                    with_cond(a, cond_first_word(kCondPolicyFused)));
-    }
     case 2: return launch(v2::lft_sweep_v2_kernel<v2::Select, 13, 4>, bytes, a);
     case 8: return launch(v2::lft_sweep_v2_kernel<v2::Chain, 13, 4>, bytes, a);
     case 10: return launch(v2::lft_sweep_v2_kernel<v2::Sched, 13, 4>, bytes, a);
@@ -4206,7 +3796,7 @@ hipError_t dispatch_lft_v2_f32(const LftArgs<float>& a, hipStream_t stream) {
   if (a.s != 13 || a.m != 4) return hipErrorNotSupported;
   const int var = g_opt_variant;
   if (opt(HOP_OPT_REFERENCE_ASSOC) ||
-      (var != 0 && var != 40 && var != 41 && (!kDevBuild || (var != 56 && var != 57 && var != 95))))
+      (var != 0 && var != 40 && var != 41 && (!kDevBuild || (var != 56 && var != 57))))
     return hipErrorNotSupported;
   using G = v2::Geo<13, 4, 4>;
   const long long blocks = (a.batch + kProbPerBlock - 1) / kProbPerBlock;
@@ -4219,8 +3809,6 @@ hipError_t dispatch_lft_v2_f32(const LftArgs<float>& a, hipStream_t stream) {
 #ifdef HOP_DEV
     if (var == 56 || var == 57)  // the predict on the f32 matrix cores (SchedCondMfma)
       return go(v2::lft_cond_kernel<v2::SchedCondMfma, 13, 4, float>);
-    if (var == 95)  // plain converting reads (the round-2 fp32-block kernel, A/B)
-      return go(v2::lft_cond_kernel<v2::SchedCond, 13, 4, float>);
 #endif
     // QT / A / B reads under the two sweeps (SchedCondL: the fp64 default's placement)
     return go(v2::lft_cond_kernel<v2::SchedCondL, 13, 4, float>);

@@ -3,7 +3,7 @@ real quadrotor linearisations (tests/real_lin.py's batch: perturbed rollouts,
 central differences, rho_reg = 1e-12).  Variant numbers need the developer
 library (HOP_LIB=time_opt_ilqr_amd/libhop_amd_dev.so); 0 = the product default.
 
-    python tools/ab_traj.py --variants 0,97 --rounds 9 --iters 10 [--system quadrotor|synthetic]
+    python tools/ab_traj.py --variants 0,40 --rounds 9 --iters 10 [--system quadrotor|synthetic]
 """
 import argparse
 import json
@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variants", default="0,97")
+    ap.add_argument("--variants", default="0,40")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--batch", type=int, default=4096)
