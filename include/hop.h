@@ -148,7 +148,12 @@ int hop_cu_fallbacks(void); /* CU-count queries that failed and assumed 256 (lay
  *   R      r_is_inverse=1: R_inv_cached;  r_is_inverse=0: raw R_k, inverted per
  *          step with chol_inv semantics.  Element (b,k) block at
  *          R + b*r_batch_stride + k*r_step_stride ([m][m]).
- *   z0     [batch or 1][s]  (z0_batch_stride = s or 0)
+ *   z0     [batch or 1][s]  (z0_batch_stride = s or 0); any vector, not only the
+ *          builders' e_s (tests/test_gpu_z0.py holds every kernel to the oracle on
+ *          dense per-problem rows).  A non-finite z0 row: that problem's J is non-finite
+ *          at every horizon (all NaN for a NaN entry, NaN or +inf for an inf entry),
+ *          status HOP_ST_NONFINITE, t_star = t_min when J[t_min - 1] is NaN; no other
+ *          problem changes.
  *   n_use  = T_use (<= n_alloc); n_use <= 0 launches nothing (reference returns [])
  *   max_tries = chol_inv jitter tries (8 = utils.py; 4 = legacy ilqr_propagator.py)
  *   J      [batch][n_use]  out: J[b][t-1] = 1/2 z0^T P0^(t) z0
@@ -159,8 +164,9 @@ int hop_cu_fallbacks(void); /* CU-count queries that failed and assumed 256 (lay
  *   dbg_prefix [batch][n_use][3][s][s] nullable: Ebar_k, Fbar_k, Gbar_k
  *   s = 13, m = 4, fp64, no debug outputs: two stream-ordered launches, the
  *          conditioned-prefix kernel (z0 folded into the prefix first, same J to
- *          ~1e-12) and a rerun of the problems it could not take with the
- *          reference association (status and failure semantics unchanged): the
+ *          ~1e-11 for any z0: DESIGN.md 3.0) and a rerun of the problems it could
+ *          not take with the reference association (status and failure semantics
+ *          unchanged): the
  *          rerun launch first resolves hand-overs explained by non-finite inputs
  *          (HOP_TRIAGE_ACCEPTS), then recomputes the rest, up to four problems per
  *          workgroup of sixteen as a pipeline over the workgroup's four waves

@@ -32,6 +32,8 @@ extern "C" {
  *   eps = 1e-9 x10 per failed factorisation up to max_tries, a pivot <= 0 or NaN
  *   rejects, then the LU slot; status bits HOP_ST_JITTER / HOP_ST_LU /
  *   HOP_ST_NONFINITE.  A non-finite block gives NaN at the horizons that read it.
+ *   A non-finite z0 row gives that problem NaN at every horizon and HOP_ST_NONFINITE
+ *   (t_star = t_min), and changes no other problem.
  *   n_use <= 0 launches nothing; n_use > n_alloc, null pointers and a bad
  *   t_min/t_max window are HOP_E_ARG.
  */

@@ -110,8 +110,10 @@ def lft_sweep(A, Bm, Q, R_inv, z0, QT, N=None, R_list=None, want_efg=False,
               want_prefix=False, max_tries=8):
     """J[t-1] for t = 1..N (horizon_selection.py:36-86), one problem.
 
-    A, Q, QT : (>=N, s, s); Bm : (>=N, s, m); R_inv : (m, m) (cached inverse)
-    or None with R_list (N, m, m) (then each stage inverse is spd_inverse(R_k)).
+    A, Q, QT : (>=N, s, s); Bm : (>=N, s, m); R_inv : (m, m) (cached inverse),
+    (>=N, m, m) (a per-step inverse: the numbers spd_inverse(R_k) of R_list gives,
+    handed in), or None with R_list (N, m, m) (then each stage inverse is
+    spd_inverse(R_k)).
     Returns dict(J, status[, E, F, G][, Ebar, Fbar, Gbar]).
     """
     N = len(A) if N is None else int(N)
@@ -130,6 +132,8 @@ def lft_sweep(A, Bm, Q, R_inv, z0, QT, N=None, R_list=None, want_efg=False,
 
     if R_inv is None:
         rinv = [inv(R_list[k]) for k in range(N)]
+    elif np.ndim(R_inv) == 3:
+        rinv = [np.asarray(R_inv[k], dtype=np.float64) for k in range(N)]
     else:
         rinv = [np.asarray(R_inv, dtype=np.float64)] * N
 
@@ -177,7 +181,8 @@ def lft_sweep(A, Bm, Q, R_inv, z0, QT, N=None, R_list=None, want_efg=False,
 
 
 def lft_sweep_batch(A, Bm, Q, R_inv, z0, QT, N=None, max_tries=8):
-    """Loop of lft_sweep over a leading batch axis.  R_inv: (m,m) or (B,m,m)."""
+    """Loop of lft_sweep over a leading batch axis.  R_inv: (m,m), (B,m,m), or per
+    step (B or 1, >=N, m, m); z0: (s,) or (B or 1, s)."""
     Bn = A.shape[0]
     N = A.shape[1] if N is None else int(N)
     J = np.zeros((Bn, N))
@@ -185,8 +190,8 @@ def lft_sweep_batch(A, Bm, Q, R_inv, z0, QT, N=None, max_tries=8):
     R_inv = np.asarray(R_inv)
     z0 = np.asarray(z0)
     for b in range(Bn):
-        r = R_inv if R_inv.ndim == 2 else R_inv[b]
-        z = z0 if z0.ndim == 1 else z0[b]
+        r = R_inv if R_inv.ndim == 2 else R_inv[b if R_inv.shape[0] > 1 else 0]
+        z = z0 if z0.ndim == 1 else z0[b if z0.shape[0] > 1 else 0]
         o = lft_sweep(A[b], Bm[b], Q[b], r, z, QT[b], N, max_tries=max_tries)
         J[b] = o["J"]
         st[b] = o["status"]
@@ -622,6 +627,81 @@ def synth_lft_batch(base_seed, B, s, m, N):
     """Stack synth_lft_problem(base_seed + i) for i < B."""
     parts = [synth_lft_problem(base_seed + i, s, m, N) for i in range(B)]
     return tuple(np.stack([p[j] for p in parts]) for j in range(7))
+
+
+Z0_KINDS = ("e_s", "dense", "offset", "last0", "big", "small", "zero", "e_0")
+
+
+def synth_z0(kinds, Bn, s, seed):
+    """(Bn, s) initial augmented states, row b of kind kinds[b % len(kinds)] (names of
+    Z0_KINDS): e_s (the builders' value, augmented.py:57), dense N(0,1),
+    [0.3 N(0,1); 1] (the caller's [x0 - X[0]; 1]), [N(0,1); 0], 1e3 x dense,
+    1e-3 x dense, all zero, e_0.  propagator_all_Jt_aug evaluates
+    1/2 z0^T P0 z0 for whatever z0 it is handed (horizon_selection.py:85)."""
+    rng = np.random.default_rng(int(seed))
+    z = np.zeros((Bn, s))
+    for b in range(Bn):
+        kind = kinds[b % len(kinds)]
+        d = rng.standard_normal(s)  # drawn for every row: row b does not depend on kinds
+        if kind == "e_s":
+            z[b, -1] = 1.0
+        elif kind == "dense":
+            z[b] = d
+        elif kind == "offset":
+            z[b, :-1], z[b, -1] = 0.3 * d[:-1], 1.0
+        elif kind == "last0":
+            z[b, :-1] = d[:-1]
+        elif kind == "big":
+            z[b] = 1e3 * d
+        elif kind == "small":
+            z[b] = 1e-3 * d
+        elif kind == "e_0":
+            z[b, 0] = 1.0
+        elif kind != "zero":
+            raise ValueError(f"unknown z0 kind {kind!r}")
+    return z
+
+
+def synth_tstar_batch(base_seed, B, s, m, N, scales=(0.0, 1.0, 3.0, 10.0)):
+    """synth_lft_batch with QT scaled by 50 and z0[b] = [c_b delta_b; 1], c_b cycling
+    over `scales`, delta_b ~ N(0,1): a batch whose minimising horizon moves across the
+    window with c_b (z0 = e_s at c = 0), so that T* equality is a real assertion."""
+    A, Bm, Q, R, Ri, z0, QT = synth_lft_batch(base_seed, B, s, m, N)
+    rng = np.random.default_rng(int(base_seed) + 977)
+    z0 = np.zeros((B, s))
+    for b in range(B):
+        z0[b, :-1] = scales[b % len(scales)] * rng.standard_normal(s - 1)
+        z0[b, -1] = 1.0
+    return A, Bm, Q, R, Ri, z0, 50.0 * QT
+
+
+def argmin_gap(J, T_min, T_max):
+    """Relative gap between the smallest and the second-smallest J of the window
+    [T_min, T_max], per row: how far T* is from a tie."""
+    win = np.sort(np.asarray(J)[..., int(T_min) - 1:int(T_max)], axis=-1)
+    return (win[..., 1] - win[..., 0]) / np.abs(win[..., 0])
+
+
+def synth_R_steps(seed, B, N, m):
+    """Per-problem, per-step control weights R[b, k] = diag(U(0.5, 2)) + 0.1 sym(N(0,1))
+    (B, N, m, m), all different, and their inverses spd_inverse(R[b, k])[0]: what
+    horizon_selection.py:52 computes from R_list[k].  A draw whose smallest eigenvalue
+    is under 0.1 (possible at m = 16) is drawn again, so every block is SPD with a
+    condition number under ~30."""
+    rng = np.random.default_rng(int(seed))
+    R = np.zeros((B, N, m, m))
+    Ri = np.zeros((B, N, m, m))
+    for b in range(B):
+        for k in range(N):
+            while True:
+                Rk = np.diag(rng.uniform(0.5, 2.0, m)) + 0.1 * sym(rng.standard_normal((m, m)))
+                if np.linalg.eigvalsh(Rk).min() >= 0.1:
+                    break
+            R[b, k] = Rk
+            Ri[b, k], st = spd_inverse(Rk)
+            if st != 0:
+                raise AssertionError("synth_R_steps: an SPD draw needed the jitter ladder")
+    return R, Ri
 
 
 def synth_riccati_problem(seed, n, m, N):

@@ -681,11 +681,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void l
     cnt += __popcll(mk[i]);
   }
   if (cnt == 0) return;  // workgroup-uniform
+  // the masks live where the rings and the body's LDS-DMA images go: every wave has
+  // read them before either branch writes there (cnt is workgroup-uniform)
+  __syncthreads();
   if (cnt > kSmallPipeMax) {
     lft_small_body<T, S, MM, false, 64, 0, 1>(a);
     return;
   }
-  __syncthreads();  // the masks live where the rings go
   T* ring = reinterpret_cast<T*>(smem_raw);
   unsigned* st_all = reinterpret_cast<unsigned*>(smem_raw + (2 * PG::RING + PG::BS) * sizeof(T));
 #pragma unroll 1

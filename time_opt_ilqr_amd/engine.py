@@ -165,6 +165,8 @@ def propagate(A, B, Q, R, z0, QT, *, n_use: Optional[int] = None, r_is_inverse: 
     """Batched LFT sweep (horizon_selection.py:36-86 for every problem of a batch).
 
     A, Q, QT : [Bn, N, s, s]   B : [Bn, N, s, m]   z0 : [s] or [Bn, s]
+               (a non-finite z0 row: that problem's J non-finite at every horizon, status
+               ST_NONFINITE, t_star = t_min on a NaN; no other problem changes)
     R        : R^-1 if r_is_inverse (R_inv_cached) else raw R_k, shaped
                [m, m] | [Bn or 1, m, m] | [Bn or 1, N, m, m] (per step)
     n_use    : T_use (default N).  t_min/t_max: fuse the argmin (solver.py:522).
