@@ -143,6 +143,23 @@ CHAIN_SIGNATURES = {
 }
 CHAIN_MAX_P = 15  # include/hop_chain.h HOP_CHAIN_MAX_P
 
+# include/hop_fleet.h (fleets of the built-in systems as device systems); bound beside the
+# others.  Every entry starts with a pointer to FleetParams; the rest is the chain entry's
+# list, with the wrap mask after the cost blocks (cost: xg bs u_ref bs Q R Qf w bs wrap)
+_FCOST = _CCOST + [_U32]
+FLEET_SIGNATURES = {
+    "hop_fleet_dynamics_f64": (C.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _I64, _P]),
+    "hop_fleet_rollout_f64": (C.c_int, [_P, _P, _I64, _P, _I64, _I32, C.c_double, _P, _P]),
+    "hop_fleet_linearize_f64": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, C.c_double,
+                                          C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
+    "hop_fleet_cost_true_f64": (C.c_int, [_P, _P, _P, _P] + _FCOST + [_I64, _I32, _P, _P]),
+    "hop_fleet_forward_workspace_bytes": (C.c_size_t, [_P, _I64, _I32, _I32]),
+    "hop_fleet_forward_linesearch_f64": (C.c_int, [_P, _P, _P] + _FCOST +
+                                         [_P, _P, _P, _P, _P, _I32, _I64, _I32, _P, C.c_size_t,
+                                          _P, _P, _P, _P, _P, _P]),
+}
+FLEET_MAX_N, FLEET_MAX_M = 31, 16  # include/hop_fleet.h HOP_FLEET_MAX_N, HOP_FLEET_MAX_M
+
 # include/hop_onepass.h (the one-pass window method's primitives); bound beside the others
 ONEPASS_SIGNATURES = {
     # system X U cost T_min T_max batch N J T_bar stream
@@ -180,6 +197,11 @@ class ChainParams(C.Structure):
                 ("ks", C.c_double), ("c", C.c_double)]
 
 
+class FleetParams(C.Structure):
+    """hop_fleet_params (include/hop_fleet.h)."""
+    _fields_ = [("system", _I32), ("count", _I32), ("dt", C.c_double)]
+
+
 _lock = threading.Lock()
 _lib = None
 
@@ -208,6 +230,7 @@ def load(path: str | None = None):
         for name, (res, args) in (list(SIGNATURES.items()) + list(WIDE_SIGNATURES.items())
                                   + list(WIDE_JCURVE_SIGNATURES.items())
                                   + list(CHAIN_SIGNATURES.items())
+                                  + list(FLEET_SIGNATURES.items())
                                   + list(ONEPASS_SIGNATURES.items())
                                   + list(TESTHOOK_SIGNATURES.items())):
             if other and not hasattr(lib, name):

@@ -819,12 +819,40 @@ def _chain_params(system):
     return _lib.ChainParams(int(p), int(m), float(dt), float(k), float(ks), float(c))
 
 
-def _chain_cost_args(cost, Bn, n, m, dev):
-    """hop_chain.h's cost arguments (xg bs u_ref bs Q R Qf w bs) of a CostParams."""
+def is_fleet(system) -> bool:
+    """True for a systems.Fleet: `count` copies of one built-in system stacked
+    member-major (include/hop_fleet.h); dynamics, rollout, linearize, cost_true and
+    forward_linesearch take it as ``system`` and step with its own dt."""
+    return getattr(system, "fleet_params", None) is not None
+
+
+def is_object_system(system) -> bool:
+    """a device system that is passed as the object itself: a spring chain or a fleet"""
+    return is_chain(system) or is_fleet(system)
+
+
+def _fleet_params(system):
+    sid, count, dt = system.fleet_params()
+    return _lib.FleetParams(int(sid), int(count), float(dt))
+
+
+def _object_entry(system, name):
+    """(hop_chain_<name> or hop_fleet_<name>, its parameter struct) of an object system"""
+    lib = _lib.load()
+    if is_fleet(system):
+        return getattr(lib, "hop_fleet_" + name), _fleet_params(system)
+    return getattr(lib, "hop_chain_" + name), _chain_params(system)
+
+
+def _chain_cost_args(cost, Bn, n, m, dev, system=None):
+    """hop_chain.h's cost arguments (xg bs u_ref bs Q R Qf w bs) of a CostParams; for a
+    fleet hop_fleet.h's, which end in the wrap mask."""
     torch = _torch()
+    fleet = is_fleet(system)
+    what = "fleet" if fleet else "spring chain"
     if cost.obstacles is not None and len(cost.obstacles):
-        raise ValueError("a spring chain takes no obstacle table (it has no planar position)")
-    if cost.wrap_idx is not None and len(cost.wrap_idx):
+        raise ValueError(f"a {what} takes no obstacle table")
+    if not fleet and cost.wrap_idx is not None and len(cost.wrap_idx):
         raise ValueError("a spring chain has no angle states: wrap_idx must be empty")
     dt = torch.float64
     xg = _dev(cost.xg, "xg", dt, dev)
@@ -833,7 +861,7 @@ def _chain_cost_args(cost, Bn, n, m, dev):
     w = _scalar_or_vec(cost.w, dt, dev, "w")
     for t, nm, shp in ((Q, "Q", (n, n)), (R, "R", (m, m)), (Qf, "Qf", (n, n))):
         if tuple(t.shape) != shp:
-            raise ValueError(f"spring chain: {nm} must be one {shp} block shared by the batch, "
+            raise ValueError(f"{what}: {nm} must be one {shp} block shared by the batch, "
                              f"got {tuple(t.shape)}")
     for t, nm, shp in ((xg, "xg", (n,)), (u_ref, "u_ref", (m,))):
         if tuple(t.shape[-1:]) != shp:
@@ -843,12 +871,14 @@ def _chain_cost_args(cost, Bn, n, m, dev):
     args = [_lib.ptr(xg), _bstride(xg, 1, "xg", Bn), _lib.ptr(u_ref),
             _bstride(u_ref, 1, "u_ref", Bn), _lib.ptr(Q), _lib.ptr(R), _lib.ptr(Qf),
             _lib.ptr(w), 0 if w.numel() == 1 else 1]
+    if fleet:
+        args.append(wrap_mask(cost.wrap_idx, n))
     return args, (xg, u_ref, Q, R, Qf, w)
 
 
 def system_dims(system) -> tuple:
-    """(n, m) of a system id or name (hop_system_dims), or of a spring chain."""
-    if is_chain(system):
+    """(n, m) of a system id or name (hop_system_dims), of a spring chain or of a fleet."""
+    if is_object_system(system):
         return int(system.n), int(system.m)
     sid = system_id(system)
     n, m = _lib.C.c_int32(), _lib.C.c_int32()
@@ -894,10 +924,11 @@ def linearize(system, X, U, dt: float, *, central: bool = False, n_use: Optional
     U = _dev(U, "U", torch.float64, X.device)
     if X.dim() == 2:  # one problem [N+1, n]: a batch of one (both layouts)
         X, U = X[None], U[None]
-    chain = is_chain(system)
+    chain = is_object_system(system)
     if tile64:
         if chain:
-            raise ValueError("a spring chain has no tile64 outputs (batch-major fp64 only)")
+            raise ValueError("a spring chain or fleet has no tile64 outputs (batch-major fp64 "
+                             "only)")
         return _linearize_tile64(system, X, U, dt, central, n_use, epsx, epsu, relx, relu,
                                  tile64_dtype or torch.float64)
     sid = getattr(system, "name", "chain") if chain else system_id(system)
@@ -918,8 +949,8 @@ def linearize(system, X, U, dt: float, *, central: bool = False, n_use: Optional
     tail = (Bn, N, n_use, int(bool(central)), float(epsx), float(epsu), float(relx), float(relu),
             _lib.ptr(A), _lib.ptr(Bm), _lib.ptr(a_res), _lib.ptr(Fx), _lib.stream_handle(dev))
     if chain:
-        rc = _lib.load().hop_chain_linearize_f64(_lib.C.byref(_chain_params(system)), _lib.ptr(X),
-                                                 _lib.ptr(U), *tail)
+        fn, par = _object_entry(system, "linearize_f64")
+        rc = fn(_lib.C.byref(par), _lib.ptr(X), _lib.ptr(U), *tail)
     else:
         rc = _lib.load().hop_linearize_f64(sid, float(dt), _lib.ptr(X), _lib.ptr(U), *tail)
     _lib.check(rc)
@@ -962,7 +993,7 @@ def _linearize_tile64(system, X, U, dt, central, n_use, epsx, epsu, relx, relu, 
 def dynamics(system, X, U, dt: float):
     """x' = F(x, u) for X [..., n], U [..., m] (fp64, on the device)."""
     torch = _torch()
-    chain = is_chain(system)
+    chain = is_object_system(system)
     sid = None if chain else system_id(system)
     n, m = system_dims(system if chain else sid)
     X = _dev(X, "X", torch.float64)
@@ -973,7 +1004,8 @@ def dynamics(system, X, U, dt: float):
     out = torch.empty_like(X)
     tail = (_lib.ptr(X), n, _lib.ptr(U), m, cnt, _lib.ptr(out), n, _lib.stream_handle(X.device))
     if chain:
-        rc = _lib.load().hop_chain_dynamics_f64(_lib.C.byref(_chain_params(system)), *tail)
+        fn, par = _object_entry(system, "dynamics_f64")
+        rc = fn(_lib.C.byref(par), *tail)
     else:
         rc = _lib.load().hop_dynamics_f64(sid, float(dt), *tail)
     _lib.check(rc)
@@ -1030,7 +1062,7 @@ class CostParams:
 
 
 def _traj_xu(system, X, U):
-    sid = system if is_chain(system) else system_id(system)  # a chain stays the object
+    sid = system if is_object_system(system) else system_id(system)  # stays the object
     n, m = system_dims(sid)
     torch = _torch()
     X = _dev(X, "X", torch.float64)
@@ -1045,7 +1077,7 @@ def _traj_xu(system, X, U):
 def rollout(system, x0, U, dt: float, *, max_state_norm: float = 1e6):
     """Batched rollout (solver.py:42-62): x0 [n] or [B, n], U [B, N, m] -> X [B, N+1, n]."""
     torch = _torch()
-    chain = is_chain(system)
+    chain = is_object_system(system)
     sid = system if chain else system_id(system)
     n, m = system_dims(sid)
     U = _dev(U, "U", torch.float64)
@@ -1061,7 +1093,8 @@ def rollout(system, x0, U, dt: float, *, max_state_norm: float = 1e6):
     tail = (_lib.ptr(x0), x_bs, _lib.ptr(U), Bn, N, float(max_state_norm), _lib.ptr(X),
             _lib.stream_handle(dev))
     if chain:
-        rc = _lib.load().hop_chain_rollout_f64(_lib.C.byref(_chain_params(system)), *tail)
+        fn, par = _object_entry(system, "rollout_f64")
+        rc = fn(_lib.C.byref(par), *tail)
     else:
         rc = _lib.load().hop_rollout_f64(sid, float(dt), *tail)
     _lib.check(rc)
@@ -1076,11 +1109,11 @@ def cost_true(system, X, U, T_star, cost: CostParams):
     T = _dev(torch.as_tensor(T_star, device=dev).to(torch.int32).reshape(-1).expand(Bn),
              "T_star")
     J = torch.empty((Bn,), dtype=torch.float64, device=dev)
-    if is_chain(sid):
-        cargs, keep = _chain_cost_args(cost, Bn, n, m, dev)
-        rc = _lib.load().hop_chain_cost_true_f64(
-            _lib.C.byref(_chain_params(sid)), _lib.ptr(X), _lib.ptr(U), _lib.ptr(T), *cargs, Bn, N,
-            _lib.ptr(J), _lib.stream_handle(dev))
+    if is_object_system(sid):
+        cargs, keep = _chain_cost_args(cost, Bn, n, m, dev, sid)
+        fn, par = _object_entry(sid, "cost_true_f64")
+        rc = fn(_lib.C.byref(par), _lib.ptr(X), _lib.ptr(U), _lib.ptr(T), *cargs, Bn, N,
+                _lib.ptr(J), _lib.stream_handle(dev))
     else:
         cargs, keep = cost.args(Bn, n, m, dev)
         rc = _lib.load().hop_cost_true_f64(sid, _lib.ptr(X), _lib.ptr(U), _lib.ptr(T), *cargs, Bn,
@@ -1118,12 +1151,12 @@ def forward_linesearch(system, X, U, T_star, K, k, cost: CostParams, dt: float, 
     al = [float(a) for a in alphas]
     if not 1 <= len(al) <= 8:
         raise ValueError("1..8 step sizes")
-    chain = is_chain(sid)
+    chain = is_object_system(sid)
     lib = _lib.load()
     if chain:
-        cp = _chain_params(sid)
-        cargs, keep = _chain_cost_args(cost, Bn, n, m, dev)
-        ws_bytes = int(lib.hop_chain_forward_workspace_bytes(_lib.C.byref(cp), Bn, N, len(al)))
+        ws_fn, cp = _object_entry(sid, "forward_workspace_bytes")
+        cargs, keep = _chain_cost_args(cost, Bn, n, m, dev, sid)
+        ws_bytes = int(ws_fn(_lib.C.byref(cp), Bn, N, len(al)))
     else:
         cargs, keep = cost.args(Bn, n, m, dev)
         ws_bytes = int(lib.hop_forward_workspace_bytes(sid, Bn, N, len(al)))
@@ -1134,7 +1167,8 @@ def forward_linesearch(system, X, U, T_star, K, k, cost: CostParams, dt: float, 
                            torch.empty((Bn,), dtype=torch.int32, device=dev))
     c_al = (_lib.C.c_double * len(al))(*al)
     head = (_lib.C.byref(cp),) if chain else (sid, float(dt))
-    fn = lib.hop_chain_forward_linesearch_f64 if chain else lib.hop_forward_linesearch_f64
+    fn = _object_entry(sid, "forward_linesearch_f64")[0] if chain else \
+        lib.hop_forward_linesearch_f64
     rc = fn(*head, _lib.ptr(X), _lib.ptr(U), *cargs, _lib.ptr(T), _lib.ptr(act),
             _lib.ptr(K), _lib.ptr(k), c_al, len(al), Bn, N, _lib.C.c_void_p(ws.data_ptr()),
             ws_bytes, _lib.ptr(out.X), _lib.ptr(out.U), _lib.ptr(out.J), _lib.ptr(out.J_old),
@@ -1208,6 +1242,9 @@ def _onepass_system(system):
     if is_chain(system):
         raise NotImplementedError("the one-pass primitives cover the five built-in device "
                                   "systems (n <= 12), not the spring chain")
+    if is_fleet(system):
+        raise NotImplementedError("the one-pass primitives cover the five built-in device "
+                                  "systems (n <= 12), not a fleet of them")
     return system_id(system)
 
 

@@ -8,7 +8,8 @@ Same names, arguments and return shapes (lists of per-step NumPy blocks) for one
 trajectory; ``linearize_batch`` is the batched device form (torch tensors in
 HBM, the layout engine.propagate_traj / engine.riccati read).  ``F`` must be a
 :class:`~time_opt_ilqr_amd.systems.DeviceDynamics` or
-:class:`~time_opt_ilqr_amd.systems.SpringChain` (a system the kernel knows):
+:class:`~time_opt_ilqr_amd.systems.SpringChain` or :class:`~time_opt_ilqr_amd.systems.Fleet`
+(a system the kernel knows):
 an arbitrary Python callable is refused with TypeError rather than evaluated on
 the CPU.
 """
@@ -17,18 +18,18 @@ from __future__ import annotations
 import numpy as np
 
 from . import engine
-from .systems import DeviceDynamics, SpringChain
+from .systems import DeviceDynamics, Fleet, SpringChain
 
 
 def _check_F(F):
-    if not isinstance(F, (DeviceDynamics, SpringChain)):
+    if not isinstance(F, (DeviceDynamics, SpringChain, Fleet)):
         raise TypeError("F must be a time_opt_ilqr_amd.systems DeviceDynamics (the device "
                         "linearisation has no path for arbitrary Python dynamics)")
     return F
 
 
 def _sys(F):
-    return F if engine.is_chain(F) else F.system_id
+    return F if engine.is_object_system(F) else F.system_id
 
 
 def _run(F, X, U, central, epsx, epsu, relx, relu):
@@ -93,7 +94,7 @@ def extend_nominal_backward(F, X, U, u_fill, *, S_back: int, preimage_method: st
     copies, as the reference does)."""
     import torch
     F = _check_F(F)
-    if engine.is_chain(F):
+    if engine.is_object_system(F):
         raise NotImplementedError("the negative-time prefix covers the five built-in systems")
     pre = str(preimage_method).lower().strip()
     if pre != "fixedpoint":  # the reference runs its fixed-point step for any other name too

@@ -34,6 +34,9 @@ PREIMAGE_ITERS, PREIMAGE_TOL, PREIMAGE_DAMPING = 4, 1e-9, 0.5  # solver.py:636-6
 def check_scope(system, S_window, onepass_preimage, extra_stage_cost=None):
     """The inputs method="onepass" takes on the device; everything else raises here,
     before anything touches the GPU."""
+    if engine.is_fleet(system):
+        raise NotImplementedError("method='onepass' is not implemented for a fleet (the "
+                                  "one-pass primitives cover the five built-in systems)")
     if isinstance(system, host_dynamics.HostDynamics) or (
             callable(system) and not hasattr(system, "system_id") and not engine.is_chain(system)):
         raise NotImplementedError("method='onepass' runs the five built-in device systems "

@@ -100,8 +100,8 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
     leaves the host waiting only on the once-per-iteration "all done" flag).
 
     ``system`` is a device system (id, name or systems.DeviceDynamics, with ``dt``; or a
-    systems.SpringChain, which steps with its own dt and runs wide solves end to end on
-    the device) or
+    systems.SpringChain or systems.Fleet, which step with their own dt and run wide solves
+    end to end on the device) or
     a host_dynamics.HostDynamics wrapping a Python callable F(x, u): then the rollouts,
     the FD linearisation and the line search evaluate F on the host per problem (the
     reference's own call form, host_dynamics.py) and the select, Riccati and accept
@@ -128,10 +128,17 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
         if obstacles is not None and len(obstacles) > 0:
             raise ValueError("host dynamics: pass the stage cost as extra_stage_cost")
     else:
+        if engine.is_fleet(system) and extra_stage_cost is not None:
+            raise NotImplementedError("a fleet has no stage cost besides its dense Q and R "
+                                      "(wrap it in host_dynamics.HostDynamics for one)")
         if extra_stage_cost is not None:
             raise ValueError("device dynamics take the point-mass obstacles table; a "
                              "Python extra_stage_cost needs host dynamics")
-        if engine.is_chain(system):  # a systems.SpringChain: the object is the system
+        if engine.is_fleet(system):  # a systems.Fleet: the object is the system
+            if obstacles is not None and len(obstacles) > 0:
+                raise NotImplementedError("a fleet takes no obstacle table")
+            sid, dt = system, float(system.dt)  # it steps with its own dt
+        elif engine.is_chain(system):  # a systems.SpringChain: the object is the system
             if obstacles is not None and len(obstacles) > 0:
                 raise ValueError("a spring chain takes no obstacle table")
             if wrap_idx is not None and len(wrap_idx) > 0:
@@ -378,21 +385,22 @@ def _host_linesearch(system, Xh, Uh, T_star, K, k, active, cost_np, alphas, extr
 # ---------------------------------------------------------------------------
 
 def _dyn(F):
-    from .systems import DeviceDynamics, SpringChain
-    if not isinstance(F, (DeviceDynamics, SpringChain)):
-        raise TypeError("F must be a time_opt_ilqr_amd.systems.DeviceDynamics or SpringChain "
-                        "(use the systems.make_* makers)")
+    from .systems import DeviceDynamics, Fleet, SpringChain
+    if not isinstance(F, (DeviceDynamics, SpringChain, Fleet)):
+        raise TypeError("F must be a time_opt_ilqr_amd.systems.DeviceDynamics, SpringChain or "
+                        "Fleet (use the systems.make_* makers)")
     return F
 
 
 def _sys(F):
-    """what the engine takes as ``system``: a built-in system's id, a SpringChain itself"""
-    return F if engine.is_chain(F) else F.system_id
+    """what the engine takes as ``system``: a built-in system's id, a SpringChain or a
+    Fleet itself"""
+    return F if engine.is_object_system(F) else F.system_id
 
 
 def _on_device(F) -> bool:
-    from .systems import DeviceDynamics, SpringChain
-    if isinstance(F, (DeviceDynamics, SpringChain)):
+    from .systems import DeviceDynamics, Fleet, SpringChain
+    if isinstance(F, (DeviceDynamics, SpringChain, Fleet)):
         return True
     if not callable(F):
         raise TypeError("F must be a systems.DeviceDynamics or a callable F(x, u) -> x_next")
@@ -479,7 +487,7 @@ def cost_timeopt_true(X, U, xg, u_ref, Q, R, alpha, w, T_star, wrap_idx=None,
 
 
 def _system_for(system, n, m):
-    if engine.is_chain(system):
+    if engine.is_object_system(system):
         return system
     if system is not None:
         return engine.system_id(getattr(system, "system_id", system))
@@ -545,6 +553,9 @@ def ilqr_timeopt(F, x0, xg, u_ref, Q, R, alpha, w, N: int, T_min: int, T_max: in
                                   "('baseline1') and 'onepass' ('baseline2')")
     x0 = np.asarray(x0, dtype=float).reshape(1, -1)
     n = x0.shape[1]
+    if engine.is_fleet(F) and extra_stage_cost is not None:
+        raise NotImplementedError("a fleet has no stage cost besides its dense Q and R "
+                                  "(wrap it in host_dynamics.HostDynamics for one)")
     if _on_device(F) and _is_obstacle_cost(extra_stage_cost):
         F = _dyn(F)
         system, kw = _sys(F), dict(dt=F.dt, obstacles=_obstacle_rows(extra_stage_cost))

@@ -194,3 +194,182 @@ def make_spring_chain(p: int = 12, m: int = 3, dt: float = 0.1, N: int = 60, see
 MAKERS = {"double_integrator": make_double_integrator, "cartpole": make_cartpole_swingup,
           "quadrotor": make_quadrotor, "pointmass": make_pointmass_navigation,
           "segway": make_segway_balance, "spring_chain": make_spring_chain}
+
+
+# ---- fleets: `count` copies of one built-in system, coupled through the cost -------
+
+def _wrap_pi(a):
+    """utils.py:127-128: (a + pi) % (2 pi) - pi"""
+    return np.remainder(a + np.pi, 2.0 * np.pi) - np.pi
+
+
+def _np_di(x, u, dt):
+    return np.stack([x[:, 0] + dt * x[:, 1], x[:, 1] + dt * u[:, 0]], -1)
+
+
+def _np_cartpole(x, u, dt):
+    g, m_cart, m_pole, length = 9.81, 1.0, 0.1, 0.5
+    total_mass = m_cart + m_pole
+    polemass_length = m_pole * length
+    th_u = x[:, 2] - math.pi
+    costh, sinth = np.cos(th_u), np.sin(th_u)
+    temp = (u[:, 0] + polemass_length * x[:, 3] * x[:, 3] * sinth) / total_mass
+    denom = length * (4.0 / 3.0 - m_pole * costh * costh / total_mass)
+    th_acc = (g * sinth - costh * temp) / denom
+    x_acc = temp - polemass_length * th_acc * costh / total_mass
+    return np.stack([x[:, 0] + dt * x[:, 1], x[:, 1] + dt * x_acc,
+                     _wrap_pi(x[:, 2] + dt * x[:, 3]), x[:, 3] + dt * th_acc], -1)
+
+
+def _np_quadrotor(x, u, dt):
+    m, g, kv, kw = 1.0, 9.81, 0.05, 0.01
+    inertia = np.array([0.02, 0.02, 0.04])
+    with np.errstate(all="ignore"):
+        bad = ~(np.isfinite(x).all(-1) & np.isfinite(u).all(-1))
+        bad |= np.sqrt((x * x).sum(-1)) > 1e6
+        phi, th, psi, omg = x[:, 6], x[:, 7], x[:, 8], x[:, 9:12]
+        bad |= np.abs(np.cos(th)) < 1e-3
+        bad |= (np.abs(omg) > 1e3).any(-1)
+        s, c = np.sin, np.cos
+        # third column of Rb = Rz Ry Rx (the only one the thrust along e3 reaches)
+        rb = np.stack([c(psi) * s(th) * c(phi) + s(psi) * s(phi),
+                       s(psi) * s(th) * c(phi) - c(psi) * s(phi), c(th) * c(phi)], -1)
+        acc = rb * u[:, :1] / m - np.array([0.0, 0.0, g]) - kv * x[:, 3:6]
+        t, sec = np.tan(th), 1.0 / np.cos(th)
+        eulerdot = np.stack([omg[:, 0] + s(phi) * t * omg[:, 1] + c(phi) * t * omg[:, 2],
+                             c(phi) * omg[:, 1] - s(phi) * omg[:, 2],
+                             s(phi) * sec * omg[:, 1] + c(phi) * sec * omg[:, 2]], -1)
+        omgdot = (u[:, 1:4] - np.cross(omg, omg * inertia)) / inertia - kw * omg
+        xn = x + dt * np.concatenate([x[:, 3:6], acc, eulerdot, omgdot], -1)
+    return np.where(bad[:, None], np.nan, xn)
+
+
+def _np_pointmass(x, u, dt):
+    return np.stack([x[:, 0] + dt * x[:, 2], x[:, 1] + dt * x[:, 3], x[:, 2] + dt * u[:, 0],
+                     x[:, 3] + dt * u[:, 1]], -1)
+
+
+def _np_segway(x, u, dt):
+    g, r, M, m, l = 9.81, 0.15, 1.0, 2.0, 0.5  # noqa: E741
+    I = (1.0 / 3.0) * m * l * l  # noqa: E741
+    a1, a2, a3 = M + m, m * l, I + m * l * l
+    Den = a1 * a3 - a2 * a2
+    A_tau, A_th = a3 / (r * Den) - a2 / Den, -(a2 * m * g * l) / Den
+    B_tau, B_th = -a2 / (r * Den) + a1 / Den, (a1 * m * g * l) / Den
+    xdd = A_tau * u[:, 0] + A_th * x[:, 2]
+    thdd = B_tau * u[:, 0] + B_th * x[:, 2]
+    return np.stack([x[:, 0] + dt * x[:, 1], x[:, 1] + dt * xdd, _wrap_pi(x[:, 2] + dt * x[:, 3]),
+                     x[:, 3] + dt * thdd], -1)
+
+
+# per system id: (n_s, m_s, name, the maker's wrap_idx, position entries, NumPy F on rows)
+_MEMBERS = {0: (2, 1, "double_integrator", (), (0,), _np_di),
+            1: (4, 1, "cartpole", (2,), (0,), _np_cartpole),
+            2: (12, 4, "quadrotor", (6, 7, 8), (0, 1, 2), _np_quadrotor),
+            3: (4, 2, "pointmass", (), (0, 1), _np_pointmass),
+            4: (4, 1, "segway", (2,), (0,), _np_segway)}
+_MEMBER_MAKERS = {0: make_double_integrator, 1: make_cartpole_swingup, 2: make_quadrotor,
+                  3: make_pointmass_navigation, 4: make_segway_balance}
+FLEET_MAX_N, FLEET_MAX_M = 31, 16  # include/hop_fleet.h: the wide Riccati pass's limits
+
+
+class Fleet:
+    """``count`` copies of one built-in system ``base`` (a DeviceDynamics, a system id 0..4
+    or a name) as one device system (include/hop_fleet.h, csrc/fleet.hip): x = [x^0 | x^1 |
+    ...] and u = [u^0 | u^1 | ...] member-major, F the concatenation of the members' F, the
+    members coupled only through dense Q, Qf and R.  n = count n_s <= 31 and m = count m_s
+    <= 16.  The engine and solver functions take the object itself as ``system`` / ``F``; it
+    steps with the member's own dt unless ``dt`` is given.  ``wrap_idx`` holds the members'
+    angle indices, repeated per member.  Calling it evaluates a NumPy twin of F on the host
+    (one state, or stacked rows), so ``host()`` wraps the same fleet for comparison."""
+
+    def __init__(self, base, count, dt=None):
+        if isinstance(base, DeviceDynamics):
+            sid, base_dt = int(base.system_id), float(base.dt)
+        else:
+            sid = engine.system_id(base)
+            base_dt = float(_MEMBER_MAKERS[sid]()[0].dt)
+        if sid not in _MEMBERS:
+            raise ValueError(f"unknown base system {base!r}")
+        ns, ms, name, wrap, pos, f_np = _MEMBERS[sid]
+        count = int(count)
+        if count < 1:
+            raise ValueError("Fleet needs count >= 1")
+        if count * ns > FLEET_MAX_N or count * ms > FLEET_MAX_M:
+            raise ValueError(f"Fleet: {count} x {name} has n = {count * ns}, m = {count * ms}; "
+                             f"the limits are n <= {FLEET_MAX_N} and m <= {FLEET_MAX_M}")
+        self.base_id, self.count = sid, count
+        self.dt = base_dt if dt is None else float(dt)
+        if not self.dt > 0.0:
+            raise ValueError("Fleet: dt must be positive")
+        self.n_member, self.m_member = ns, ms
+        self.n, self.m = count * ns, count * ms
+        self.name = f"{name}_x{count}"
+        self.wrap_idx = [a * ns + i for a in range(count) for i in wrap]
+        self.position_idx = [a * ns + i for a in range(count) for i in pos]
+        self._f_np = f_np
+
+    def fleet_params(self):
+        """(system, count, dt): what the hop_fleet_* entries take."""
+        return self.base_id, self.count, self.dt
+
+    def __call__(self, x, u):
+        """F on the host in NumPy: x [n], u [m] -> [n], or stacked rows [K, n], [K, m]."""
+        x = np.asarray(x, dtype=float)
+        u = np.asarray(u, dtype=float)
+        one = x.ndim == 1
+        xr = x.reshape(-1, self.n_member)
+        ur = u.reshape(-1, self.m_member)
+        out = self._f_np(xr, ur, self.dt).reshape(-1, self.n)
+        return out[0] if one else out
+
+    def batch(self, X, U):
+        """x' for device tensors X [..., n], U [..., m]."""
+        return engine.dynamics(self, X, U, self.dt)
+
+    def host(self):
+        """The same fleet as a host_dynamics.HostDynamics(vectorized=True)."""
+        from .host_dynamics import HostDynamics
+        return HostDynamics(self.__call__, self.n, self.m, name=self.name + "_host",
+                            vectorized=True)
+
+
+def _blockdiag(M, count):
+    M = np.atleast_2d(np.asarray(M, dtype=float))
+    return np.kron(np.eye(count), M)
+
+
+FLEET_NOISE = {0: 0.2, 1: 0.05, 2: 0.4, 3: 0.2, 4: 0.02}  # on the position entries of x0
+
+
+def make_fleet(base, count, N=None, seed=0, coupling=0.5, w_scale=1.0, T_min=None):
+    """A joint problem of ``count`` members (tests/golden/make_golden_fleet.py's): the
+    member maker's data with its own N unless given and T_max = min(maker's, N - 5); x0 =
+    the maker's start plus FLEET_NOISE[system] N(0, 1) from ``seed`` on the position
+    entries; Q = blockdiag(Q_member) + coupling Q_member[0, 0] L with L the graph Laplacian
+    of a path over the members' first coordinates; R and the terminal weight (returned
+    expanded, [n, n]) block-diagonal; w = w_scale times the maker's.  Returns the usual
+    13-tuple with F a :class:`Fleet`."""
+    F0 = Fleet(base, 1)
+    sid = F0.base_id
+    mk = _MEMBER_MAKERS[sid]() if N is None else _MEMBER_MAKERS[sid](N=int(N))
+    Fm, x0m, xgm, urm, Qm, Rm, alpha, w, Nn, t_min, t_max = mk[:11]
+    F = Fleet(Fm, count)
+    ns = F.n_member
+    rng = np.random.default_rng(seed)
+    x0 = np.tile(np.asarray(x0m, dtype=float), F.count)
+    x0[F.position_idx] += FLEET_NOISE[sid] * rng.standard_normal(len(F.position_idx))
+    Q = _blockdiag(Qm, F.count)
+    kappa = float(coupling) * float(np.asarray(Qm)[0, 0])
+    first = [a * ns for a in range(F.count)]
+    for a, b in zip(first[:-1], first[1:]):
+        Q[a, a] += kappa
+        Q[b, b] += kappa
+        Q[a, b] -= kappa
+        Q[b, a] -= kappa
+    Qf_m = alpha * np.eye(ns) if np.ndim(alpha) == 0 else np.asarray(alpha, dtype=float)
+    return (F, x0, np.tile(np.asarray(xgm, dtype=float), F.count),
+            np.tile(np.atleast_1d(np.asarray(urm, dtype=float)), F.count), Q,
+            _blockdiag(Rm, F.count), _blockdiag(Qf_m, F.count), float(w) * float(w_scale), int(Nn),
+            int(t_min if T_min is None else T_min), int(min(t_max, Nn - 5)), list(F.wrap_idx),
+            None)
