@@ -19,7 +19,8 @@
  * Every entry validates its arguments on the host before any launch:
  *   HOP_E_SIZE (-2)  p outside [1, HOP_CHAIN_MAX_P] or m outside [1, p]
  *   HOP_E_ARG  (-1)  null pointers, n_use > n_alloc, n_alpha outside [1, 8], dt <= 0,
- *                    negative sizes or strides, a workspace that is too small
+ *                    negative sizes or strides (n_alloc < 0 too, whatever n_use is, as in
+ *                    hop_fleet.h), a workspace that is too small
  *   0, nothing launched, for batch = 0 (count = 0, n_use = 0).
  * Any batch size and any N are accepted.
  */

@@ -187,6 +187,7 @@ def test_chain_validation_without_gpu(lib):
     assert need == 4 * 5 * (1 + 11 * 24 + 10 * 3) * 8
     assert one("linesearch", ws=need - 1) == -1 and b"workspace too small" in err()
     assert all(rc == -1 for rc in _calls(lib, par, batch=-1).values())
+    assert one("linearize", n_alloc=-1, n_use=-1) == -1
     # too many rows for one launch
     assert all(rc == -2 for rc in _calls(lib, par, batch=1 << 40).values())
     # an empty batch launches nothing, with or without pointers; so does n_use = 0

@@ -28,7 +28,7 @@ if DEV:  # a separate library (load it with HOP_LIB=<path>): the product .so sta
 EXTRA = {}
 HEADERS = ["hop_device.hpp", "hop_kernels.hpp", "dpp_blocks.inc", "small_math.hpp", "wrap.hpp", "dynamics.hpp",
            "lu_pivot.hpp", "hop_wide_device.hpp", "chain_dynamics.hpp", "cost_device.hpp",
-           "onepass_pick.hpp", "fleet_math.hpp"]
+           "onepass_pick.hpp", "fleet_math.hpp", "row_system.hpp"]
 ARCH = os.environ.get("HOP_OFFLOAD_ARCH", "gfx950")
 # device code from its assembly, minus the DPP hazard pads the compiled code does not
 # need (tools/nop_elide.py); HOP_NO_ELIDE=1 compiles the plain way (hipcc -c)

@@ -348,12 +348,10 @@ __global__ __launch_bounds__(TPB) void linesearch_kernel(FwdArgs a) {
 }
 
 // pass 2: one workgroup per problem: the first alpha with J' < J_old, then the copy
-template <int SYS>
-__global__ __launch_bounds__(256) void linesearch_pick_kernel(FwdArgs a) {
-  constexpr int n = state_dim(SYS), m = control_dim(SYS);
+// (the row systems' line searches end in it too: hop_kernels.hpp, PickArgs)
+__global__ __launch_bounds__(256) void linesearch_pick_kernel(PickArgs a) {
   const long long b = blockIdx.x;
   __shared__ int s_win;
-  const int N = a.N;
   if (threadIdx.x == 0) {
     const double Jo = a.J_old[b];
     int win = -1;
@@ -371,7 +369,7 @@ __global__ __launch_bounds__(256) void linesearch_pick_kernel(FwdArgs a) {
   }
   __syncthreads();
   const int win = s_win;
-  const long long nx = (long long)(N + 1) * n, nu = (long long)N * m;
+  const long long nx = a.nx, nu = a.nu;
   const double* srcX = win >= 0 ? a.ws + (b * a.n_alpha + win) * (nx + nu) : a.X + b * nx;
   const double* srcU = win >= 0 ? srcX + nx : a.U + b * nu;
   double* dX = a.X_new + b * nx;
@@ -508,9 +506,7 @@ hipError_t launch_all(int which, const void* args, hipStream_t st) {
                              dim3((unsigned)((lanes + TPB - 1) / TPB)), dim3(TPB), 0, st, a);
           hipError_t e = hipGetLastError();
           if (e != hipSuccess) return e;
-          hipLaunchKernelGGL((linesearch_pick_kernel<SYS>), dim3((unsigned)a.batch), dim3(256), 0,
-                             st, a);
-          break;
+          return launch_linesearch_pick(pick_args_of(a, state_dim(SYS), control_dim(SYS)), st);
         }
       }
       const dim3 grid((unsigned)((lanes + TPB - 1) / TPB));
@@ -522,14 +518,19 @@ hipError_t launch_all(int which, const void* args, hipStream_t st) {
         hipLaunchKernelGGL((linesearch_kernel<SYS, false, -1>), grid, dim3(TPB), 0, st, a);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL((linesearch_pick_kernel<SYS>), dim3((unsigned)a.batch), dim3(256), 0,
-                         st, a);
+      return launch_linesearch_pick(pick_args_of(a, state_dim(SYS), control_dim(SYS)), st);
     }
   }
   return hipGetLastError();
 }
 
 }  // namespace fwd
+
+hipError_t launch_linesearch_pick(const PickArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(fwd::linesearch_pick_kernel, dim3((unsigned)a.batch), dim3(256), 0, stream,
+                     a);
+  return hipGetLastError();
+}
 
 hipError_t dispatch_forward(int sys, int which, const void* args, hipStream_t stream) {
   switch (sys) {

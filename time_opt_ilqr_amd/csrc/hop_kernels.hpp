@@ -263,6 +263,22 @@ struct AcceptArgs {
   const double* J; const int* accepted; const int* T_star;
   double* lm; int* T_bar; double* J_hist; int* T_hist; int* n_hist; int* done;
 };
+// pass 2 of every line search (forward.hip, chain.hip, fleet.hip): per problem the
+// first step size with J' < J_old, then the copy of its workspace row [X' | U'] (or of
+// X, U when none was accepted); nx = (N + 1) n and nu = N m are the row lengths
+struct PickArgs {
+  const double* X; const double* U; const int* active;
+  const double* Jc; const double* ws; const double* J_old;
+  double* X_new; double* U_new; double* J; int* accepted;
+  int n_alpha;
+  long long batch, nx, nu;
+};
+template <class Fwd>  // FwdArgs or a row system's FwdC
+PickArgs pick_args_of(const Fwd& a, int n, int m) {
+  return {a.X, a.U, a.active, a.Jc, a.ws, a.J_old, a.X_new, a.U_new, a.J, a.accepted,
+          a.n_alpha, a.batch, (long long)(a.N + 1) * n, (long long)a.N * m};
+}
+hipError_t launch_linesearch_pick(const PickArgs& a, hipStream_t stream);
 hipError_t dispatch_forward(int sys, int which, const void* args, hipStream_t stream);
 hipError_t dispatch_obstacle(const ObstacleArgs& a, hipStream_t stream);
 hipError_t dispatch_accept(const AcceptArgs& a, hipStream_t stream);

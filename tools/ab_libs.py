@@ -1,5 +1,6 @@
 """Same-process interleaved A/B of two (or more) builds of libhop_amd.so on the bench
-workloads (config 3 tile64 fp32, config 2 fp64, config 4 shard, Riccati mode 0/1):
+workloads (config 3 tile64 fp32, config 2 fp64, config 4 shard, Riccati mode 0/1, the
+forward pass, and the row-layout device systems' four entries: row_system_workloads):
 
     python tools/ab_libs.py time_opt_ilqr_amd/libhop_amd.so <other.so> [--rounds 7]
 
@@ -16,6 +17,60 @@ import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _flat(out):
+    """every output of a workload as one fp64 vector (a workload returns a tensor or a
+    tuple of them), so that all of them are compared"""
+    import torch
+    outs = out if isinstance(out, (tuple, list)) else (out,)
+    return torch.cat([o.to(torch.float64).reshape(-1) for o in outs]).clone()
+
+
+def row_system_workloads(work, dev, kw):
+    """rollout, central linearisation, cost_true and forward_linesearch of the row-layout
+    device systems (csrc/row_system.hpp) at B = 4096: the chain of tools/bench_chain.py
+    (p = 12, m = 3, N = 60) and the fleets of tools/bench_fleet.py (quadrotor x 2 at
+    N = 80, double integrator x 15 at N = 60); every output of every entry."""
+    import torch
+    from time_opt_ilqr_amd import engine, systems
+    from time_opt_ilqr_amd.utils import as_terminal_weight
+    Bn = 4096
+    tt = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)  # noqa: E731
+    ch = systems.make_spring_chain(12, 3, N=60, seed=4024)
+    problems = {"chain": (ch[0], ch[1], ch[2], ch[3], ch[4], ch[5], as_terminal_weight(ch[6], 24),
+                          ch[7], 60, 55, None, 0.1)}
+    for tag, base, count, N in (("fleet_quad2", "quadrotor", 2, 80),
+                                ("fleet_di15", "double_integrator", 15, 60)):
+        F, x0, xg, ur, Q, R, Qf, w, N, _, T_max, wrap, _ = systems.make_fleet(
+            base, count, N=N, seed=7000, w_scale=100.0)
+        problems[tag] = (F, x0, xg, ur, Q, R, Qf, w, N, T_max, wrap, 0.05)
+    for tag, (F, x0, xg, ur, Q, R, Qf, w, N, T_max, wrap, du) in problems.items():
+        n, m = engine.system_dims(F)
+        x0b = tt(x0) + 0.05 * torch.randn((Bn, n), **kw)
+        U = tt(ur) + du * torch.randn((Bn, N, m), **kw)
+        X = engine.rollout(F, x0b, U, F.dt)
+        lin = engine.linearize(F, X, U, F.dt, central=True)
+        T = torch.full((Bn,), T_max, dtype=torch.int32, device=dev)
+        ric = engine.riccati(lin.A, lin.B, X, U, tt(xg), tt(ur), tt(Q), tt(R), tt(Qf), T, 1e-3,
+                             mode=0, reg_max_tries=1, wrap_idx=wrap)
+        K, k = ric.K.clone(), ric.k.clone()
+        K[:, T_max:], k[:, T_max:] = 0.0, 0.0
+        cost = engine.CostParams(tt(xg), tt(ur), tt(Q), tt(R), tt(Qf), float(w), None, wrap)
+
+        def linearize(F=F, X=X, U=U):
+            r = engine.linearize(F, X, U, F.dt, central=True)
+            return r.A, r.B, r.a_res
+
+        def linesearch(F=F, X=X, U=U, T=T, K=K, k=k, cost=cost):
+            r = engine.forward_linesearch(F, X, U, T, K, k, cost, F.dt)
+            return r.X, r.U, r.J, r.J_old, r.accepted
+
+        work[f"{tag}_rollout"] = lambda F=F, x0b=x0b, U=U: engine.rollout(F, x0b, U, F.dt)
+        work[f"{tag}_linearize_central"] = linearize
+        work[f"{tag}_cost_true"] = (lambda F=F, X=X, U=U, T=T, cost=cost:
+                                    engine.cost_true(F, X, U, T, cost))
+        work[f"{tag}_linesearch"] = linesearch
 
 
 def main():
@@ -88,8 +143,10 @@ def main():
     lcost = engine.CostParams(tt(lxg), tt(lur), tt(lQ), tt(lR), tt(lQf), lw, None, lwrap)
     lXt, lUt, lKt, lkt = tt(lX), tt(lU), tt(lK), tt(lk)
     lT = torch.full((4096,), 100, dtype=torch.int32, device=dev)
-    work["linesearch_quad"] = lambda: engine.forward_linesearch(2, lXt, lUt, lT, lKt, lkt, lcost,
-                                                                Fq.dt).X
+    def linesearch_quad():  # the narrow path through the pick kernel the row systems share
+        r = engine.forward_linesearch(2, lXt, lUt, lT, lKt, lkt, lcost, Fq.dt)
+        return r.X, r.U, r.J, r.J_old, r.accepted
+    work["linesearch_quad"] = linesearch_quad
     lin = engine.linearize(2, Xq, Uq, F.dt)
     P = tt(lQf)
     work["augment_quad"] = lambda: engine.augment(lin.A, lin.B, lin.a_res, Xq, Uq, tt(lxg),
@@ -98,6 +155,7 @@ def main():
     # kernel of the libraries before it); synthetic SPD blocks, N = 200
     s5 = synth.device_batch(4096, 5, 1, 200, seed=6, device=dev)
     work["small_s5_f64_4096"] = lambda: engine.propagate(*s5, t_min=40, t_max=200).J
+    row_system_workloads(work, dev, kw)
     if args.only:
         work = {w: f for w, f in work.items() if w in args.only.split(",")}
     L = len(libs)
@@ -106,7 +164,7 @@ def main():
     for i in range(L):  # warm-up + outputs
         _lib._lib = libs[i]
         for w, f in work.items():
-            outs[(w, i)] = f().clone()
+            outs[(w, i)] = _flat(f())
     torch.cuda.synchronize()
     for rnd in range(args.rounds):
         for w, f in work.items():
@@ -138,8 +196,10 @@ def main():
                   for i in range(L)}
         geo = {os.path.basename(args.libs[i]): round(math.exp(statistics.mean(
             [math.log(a / b) for a, b in zip(times[(w, i)], times[(w, 0)])])), 4) for i in range(L)}
+        # the first library's own round-to-round spread: what a ratio has to beat
+        spread = round((max(times[(w, 0)]) - min(times[(w, 0)])) / statistics.median(times[(w, 0)]), 4)
         print(json.dumps({"workload": w, "ms": r, "min_ms": lo, "ratio_to_first": ratio,
-                          "geomean_ratio_to_first": geo,
+                          "geomean_ratio_to_first": geo, "spread_of_first": spread,
                           "bitwise_equal": same,
                           "rounds": rounds}), flush=True)
 
