@@ -160,6 +160,20 @@ FLEET_SIGNATURES = {
 }
 FLEET_MAX_N, FLEET_MAX_M = 31, 16  # include/hop_fleet.h HOP_FLEET_MAX_N, HOP_FLEET_MAX_M
 
+# include/hop_fleet_proximity.h (the fleets' proximity cost); bound beside the others.  The
+# cost and line-search entries are hop_fleet.h's lists with a pointer to FleetProximity after
+# the wrap mask
+FLEET_PROXIMITY_SIGNATURES = {
+    # params prox X x_stride count c cx cxx stream
+    "hop_fleet_proximity_taylor_f64": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "hop_fleet_prox_cost_true_f64": (C.c_int, [_P, _P, _P, _P] + _FCOST + [_P] +
+                                     [_I64, _I32, _P, _P]),
+    "hop_fleet_prox_forward_linesearch_f64": (C.c_int, [_P, _P, _P] + _FCOST + [_P] +
+                                              [_P, _P, _P, _P, _P, _I32, _I64, _I32, _P,
+                                               C.c_size_t, _P, _P, _P, _P, _P, _P]),
+}
+FLEET_MAX_OBSTACLES = 16  # include/hop_fleet_proximity.h HOP_FLEET_MAX_OBSTACLES
+
 # include/hop_onepass.h (the one-pass window method's primitives); bound beside the others
 ONEPASS_SIGNATURES = {
     # system X U cost T_min T_max batch N J T_bar stream
@@ -202,6 +216,12 @@ class FleetParams(C.Structure):
     _fields_ = [("system", _I32), ("count", _I32), ("dt", C.c_double)]
 
 
+class FleetProximity(C.Structure):
+    """hop_fleet_proximity (include/hop_fleet_proximity.h)."""
+    _fields_ = [("obstacles", _P), ("n_obs", _I32), ("sep_radius", C.c_double),
+                ("sep_weight", C.c_double)]
+
+
 _lock = threading.Lock()
 _lib = None
 
@@ -231,6 +251,7 @@ def load(path: str | None = None):
                                   + list(WIDE_JCURVE_SIGNATURES.items())
                                   + list(CHAIN_SIGNATURES.items())
                                   + list(FLEET_SIGNATURES.items())
+                                  + list(FLEET_PROXIMITY_SIGNATURES.items())
                                   + list(ONEPASS_SIGNATURES.items())
                                   + list(TESTHOOK_SIGNATURES.items())):
             if other and not hasattr(lib, name):

@@ -24,6 +24,9 @@
 // Linearisation: lane a evaluates member a's base point and finite-difference columns
 // (fleet_math.hpp, linearize.hip's arithmetic) and writes rows [a n_s, (a + 1) n_s) of
 // A_k and B_k in full, the off-block entries by the reference's rule.
+//
+// The proximity cost (include/hop_fleet_proximity.h) is fleet_proximity.hpp, included below:
+// FleetProxRow<SYS>, the policy with the cost in stage_inc, and the Taylor kernel.
 #include "row_system.hpp"
 #include "fleet_math.hpp"
 #include "../../include/hop_fleet.h"
@@ -305,10 +308,16 @@ int with_fleet(const hop_fleet_params* q, F&& f) {
 }  // namespace fleet
 }  // namespace hop
 
+// the proximity cost: FleetProxRow<SYS> and the Taylor kernel (hop_fleet_proximity.h)
+#include "../../include/hop_fleet_proximity.h"
+#include "fleet_proximity.hpp"
+
 // ---------------------------------------------------------------- C entries
 namespace rowsys = hop::rowsys;
 using hop::fleet::Par;
+using hop::fleet::ProxPar;
 using hop::fleet::with_fleet;
+using hop::fleet::with_fleet_prox;
 
 extern "C" {
 
@@ -378,6 +387,48 @@ int hop_fleet_forward_linesearch_f64(const hop_fleet_params* params, const doubl
   const rowsys::CostC cost{xg, xg_batch_stride, u_ref, u_ref_batch_stride, Q, R, Qf, w,
                            w_batch_stride, wrap_mask};
   return with_fleet(params, [&](auto s, const Par& P) {
+    return rowsys::linesearch_entry<decltype(s)>(P, X, U, cost, T_star, active, K, k, alphas,
+                                                 n_alpha, batch, N, workspace, workspace_bytes,
+                                                 X_new, U_new, J, J_old, accepted, stream);
+  });
+}
+
+// ---- include/hop_fleet_proximity.h
+int hop_fleet_proximity_taylor_f64(const hop_fleet_params* params,
+                                   const hop_fleet_proximity* prox, const double* X,
+                                   int64_t x_stride, int64_t count, double* c, double* cx,
+                                   double* cxx, void* stream) {
+  return with_fleet_prox(params, prox, [&](auto s, const ProxPar& P) {
+    return hop::fleet::taylor_entry<hop::fleet::sys_of<typename decltype(s)::Base>::value>(
+        P, X, x_stride, count, c, cx, cxx, stream);
+  });
+}
+
+int hop_fleet_prox_cost_true_f64(const hop_fleet_params* params, const double* X,
+                                 const double* U, const int32_t* T_star, const double* xg,
+                                 int64_t xg_batch_stride, const double* u_ref,
+                                 int64_t u_ref_batch_stride, const double* Q, const double* R,
+                                 const double* Qf, const double* w, int64_t w_batch_stride,
+                                 uint32_t wrap_mask, const hop_fleet_proximity* prox,
+                                 int64_t batch, int32_t N, double* J, void* stream) {
+  const rowsys::CostC cost{xg, xg_batch_stride, u_ref, u_ref_batch_stride, Q, R, Qf, w,
+                           w_batch_stride, wrap_mask};
+  return with_fleet_prox(params, prox, [&](auto s, const ProxPar& P) {
+    return rowsys::cost_entry<decltype(s)>(P, X, U, T_star, cost, batch, N, J, stream);
+  });
+}
+
+int hop_fleet_prox_forward_linesearch_f64(
+    const hop_fleet_params* params, const double* X, const double* U, const double* xg,
+    int64_t xg_batch_stride, const double* u_ref, int64_t u_ref_batch_stride, const double* Q,
+    const double* R, const double* Qf, const double* w, int64_t w_batch_stride,
+    uint32_t wrap_mask, const hop_fleet_proximity* prox, const int32_t* T_star,
+    const int32_t* active, const double* K, const double* k, const double* alphas,
+    int32_t n_alpha, int64_t batch, int32_t N, void* workspace, size_t workspace_bytes,
+    double* X_new, double* U_new, double* J, double* J_old, int32_t* accepted, void* stream) {
+  const rowsys::CostC cost{xg, xg_batch_stride, u_ref, u_ref_batch_stride, Q, R, Qf, w,
+                           w_batch_stride, wrap_mask};
+  return with_fleet_prox(params, prox, [&](auto s, const ProxPar& P) {
     return rowsys::linesearch_entry<decltype(s)>(P, X, U, cost, T_star, active, K, k, alphas,
                                                  n_alpha, batch, N, workspace, workspace_bytes,
                                                  X_new, U_new, J, J_old, accepted, stream);

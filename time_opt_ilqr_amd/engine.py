@@ -844,6 +844,58 @@ def _object_entry(system, name):
     return getattr(lib, "hop_chain_" + name), _chain_params(system)
 
 
+def fleet_proximity(system):
+    """the systems.Proximity of a fleet that carries one, else None"""
+    return getattr(system, "proximity", None) if is_fleet(system) else None
+
+
+def _proximity_struct(system, dev):
+    """(hop_fleet_proximity of a fleet's cost, the device table it points to)"""
+    torch = _torch()
+    prox = fleet_proximity(system)
+    rows = prox.table(int(system.pos_dim))
+    tab = None
+    if len(rows):  # uploaded once per device and kept on the Proximity
+        cache = prox.__dict__.setdefault("_device_tables", {})
+        tab = cache.get(str(dev))
+        if tab is None:
+            tab = cache[str(dev)] = torch.as_tensor(rows.tolist(), dtype=torch.float64,
+                                                    device=dev)
+    radius, weight = prox.sep()
+    par = _lib.FleetProximity(None if tab is None else tab.data_ptr(), len(rows), float(radius),
+                              float(weight))
+    return par, tab
+
+
+def fleet_proximity_cost(fleet, X, want=("c", "cx", "cxx")):
+    """A fleet's proximity cost (systems.Proximity, include/hop_fleet_proximity.h) and its
+    second-order Taylor terms at every state row of X [..., n]: returns (c [...],
+    cx [..., n], cxx [..., n, n]) (entries not in `want` are None) -- the counterpart of
+    obstacle_cost, and what the select and Riccati entries take as c_extra / qx_extra /
+    qxx_extra.  cxx is the positive semidefinite part c d d^T / r^4 of the bumps' Hessians."""
+    torch = _torch()
+    if fleet_proximity(fleet) is None:
+        raise ValueError("fleet_proximity_cost needs a systems.Fleet with a proximity cost")
+    X = _dev(X, "X", torch.float64)
+    dev = X.device
+    n = int(fleet.n)
+    if X.shape[-1] != n:
+        raise ValueError(f"X must end in {n}")
+    rows = X.reshape(-1, n)
+    lead = tuple(X.shape[:-1])
+    c = torch.empty(lead, dtype=torch.float64, device=dev) if "c" in want else None
+    cx = torch.empty(lead + (n,), dtype=torch.float64, device=dev) if "cx" in want else None
+    cxx = torch.empty(lead + (n, n), dtype=torch.float64, device=dev) if "cxx" in want else None
+    par, tab = _proximity_struct(fleet, dev)
+    fp = _fleet_params(fleet)
+    rc = _lib.load().hop_fleet_proximity_taylor_f64(
+        _lib.C.byref(fp), _lib.C.byref(par), _lib.ptr(rows), n, rows.shape[0], _lib.ptr(c),
+        _lib.ptr(cx), _lib.ptr(cxx), _lib.stream_handle(dev))
+    _lib.check(rc)
+    del tab
+    return c, cx, cxx
+
+
 def _chain_cost_args(cost, Bn, n, m, dev, system=None):
     """hop_chain.h's cost arguments (xg bs u_ref bs Q R Qf w bs) of a CostParams; for a
     fleet hop_fleet.h's, which end in the wrap mask."""
@@ -1109,7 +1161,14 @@ def cost_true(system, X, U, T_star, cost: CostParams):
     T = _dev(torch.as_tensor(T_star, device=dev).to(torch.int32).reshape(-1).expand(Bn),
              "T_star")
     J = torch.empty((Bn,), dtype=torch.float64, device=dev)
-    if is_object_system(sid):
+    if fleet_proximity(sid) is not None:  # the fleet's entry with the proximity cost
+        cargs, keep = _chain_cost_args(cost, Bn, n, m, dev, sid)
+        px, tab = _proximity_struct(sid, dev)
+        keep += (tab,)
+        rc = _lib.load().hop_fleet_prox_cost_true_f64(
+            _lib.C.byref(_fleet_params(sid)), _lib.ptr(X), _lib.ptr(U), _lib.ptr(T), *cargs,
+            _lib.C.byref(px), Bn, N, _lib.ptr(J), _lib.stream_handle(dev))
+    elif is_object_system(sid):
         cargs, keep = _chain_cost_args(cost, Bn, n, m, dev, sid)
         fn, par = _object_entry(sid, "cost_true_f64")
         rc = fn(_lib.C.byref(par), _lib.ptr(X), _lib.ptr(U), _lib.ptr(T), *cargs, Bn, N,
@@ -1169,6 +1228,11 @@ def forward_linesearch(system, X, U, T_star, K, k, cost: CostParams, dt: float, 
     head = (_lib.C.byref(cp),) if chain else (sid, float(dt))
     fn = _object_entry(sid, "forward_linesearch_f64")[0] if chain else \
         lib.hop_forward_linesearch_f64
+    if fleet_proximity(sid) is not None:  # the fleet's entry with the proximity cost
+        px, tab = _proximity_struct(sid, dev)
+        keep += (tab,)
+        cargs = cargs + [_lib.C.byref(px)]
+        fn = lib.hop_fleet_prox_forward_linesearch_f64
     rc = fn(*head, _lib.ptr(X), _lib.ptr(U), *cargs, _lib.ptr(T), _lib.ptr(act),
             _lib.ptr(K), _lib.ptr(k), c_al, len(al), Bn, N, _lib.C.c_void_p(ws.data_ptr()),
             ws_bytes, _lib.ptr(out.X), _lib.ptr(out.U), _lib.ptr(out.J), _lib.ptr(out.J_old),

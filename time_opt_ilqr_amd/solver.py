@@ -107,7 +107,10 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
     reference's own call form, host_dynamics.py) and the select, Riccati and accept
     steps stay on the device.  ``extra_stage_cost``: a Python callable (x, u) ->
     (c, cx, cxx) evaluated on the host the same way (host systems only; the device
-    systems take the point-mass ``obstacles`` table).
+    systems take the point-mass ``obstacles`` table).  A systems.Fleet built with a
+    systems.Proximity carries its stage cost itself: its Taylor terms
+    (engine.fleet_proximity_cost) feed the select under both methods and the Riccati pass,
+    and the line search evaluates it at every candidate's state, all on the device.
     """
     if method == "onepass":
         from . import onepass
@@ -129,8 +132,9 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
             raise ValueError("host dynamics: pass the stage cost as extra_stage_cost")
     else:
         if engine.is_fleet(system) and extra_stage_cost is not None:
-            raise NotImplementedError("a fleet has no stage cost besides its dense Q and R "
-                                      "(wrap it in host_dynamics.HostDynamics for one)")
+            raise NotImplementedError("a fleet takes no Python stage cost: give it a "
+                                      "systems.Proximity, or wrap it in "
+                                      "host_dynamics.HostDynamics")
         if extra_stage_cost is not None:
             raise ValueError("device dynamics take the point-mass obstacles table; a "
                              "Python extra_stage_cost needs host dynamics")
@@ -147,6 +151,8 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
         else:
             sid = engine.system_id(system)
         n, m = engine.system_dims(sid)
+    # a fleet with a systems.Proximity: engine.forward_linesearch runs its proximity entry
+    prox = not host and engine.fleet_proximity(sid) is not None
     dev = device or torch.device("cuda", torch.cuda.current_device())
     f64 = torch.float64
     tt = lambda a: torch.as_tensor(np.asarray(a, dtype=float) if not isinstance(  # noqa: E731
@@ -251,6 +257,9 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
         ex = {}
         if obs is not None:
             c, cx, cxx = engine.obstacle_cost(s.X[:, :N], obs)
+            ex = dict(qxx_extra=cxx, qx_extra=cx, c_extra=c)
+        elif prox:  # a fleet's proximity cost: its Taylor terms feed the select and Riccati
+            c, cx, cxx = engine.fleet_proximity_cost(sid, s.X[:, :N])
             ex = dict(qxx_extra=cxx, qx_extra=cx, c_extra=c)
         elif host and extra_stage_cost is not None:
             parts = [host_dynamics.stage_cost_terms(extra_stage_cost, Xh[b], Uh[b])

@@ -273,6 +273,76 @@ _MEMBER_MAKERS = {0: make_double_integrator, 1: make_cartpole_swingup, 2: make_q
 FLEET_MAX_N, FLEET_MAX_M = 31, 16  # include/hop_fleet.h: the wide Riccati pass's limits
 
 
+PROXIMITY_MAX_OBSTACLES = 16  # include/hop_fleet_proximity.h HOP_FLEET_MAX_OBSTACLES
+
+
+class Proximity:
+    """A fleet's proximity cost (include/hop_fleet_proximity.h): Gaussian bumps
+    g(d; r, w) = w exp(-|d|^2 / (2 r^2)) on the members' positions p_a (the leading ``pd``
+    entries of a member's state: 1 for DI, cart-pole and segway, 2 for the point mass, 3 for
+    the quadrotor).
+
+    ``obstacles`` [K, pd + 2] (centre, radius, weight), K <= 16: g(p_a - o; r, w) for every
+    member and row.  ``separation`` (radius, weight) or None: g(p_a - p_b; r_s, w_s) for every
+    pair a < b.  Radii must be > 0 and weights finite and >= 0; the column count is checked
+    against the fleet's ``pd`` when the object is attached (``Fleet(..., proximity=...)``).
+
+    The second-order term is the positive semidefinite part of a bump's Hessian,
+    c d d^T / r^4: the -c I / r^2 term is left out on purpose, so it is not the full Hessian
+    of the point-mass obstacle cost (``obstacle_stage_cost``).  With the full Hessian the
+    reference's brute-force J curve loses definiteness at useful weights and the
+    propagator's J curve flattens until the selected horizon jumps between T_min and T_max.
+
+    The LFT select inverts Q_k + cxx.  A Q that is zero on the position entries, as the
+    point-mass maker's is, makes the select degenerate once a rank-one cxx is added: give
+    the positions weight.  A fleet's ``obstacles=`` keyword (the point-mass table with the
+    full Hessian) stays NotImplementedError."""
+
+    def __init__(self, obstacles=None, separation=None):
+        obs = np.zeros((0, 0)) if obstacles is None else np.array(obstacles, dtype=float)
+        if obs.size == 0:
+            obs = np.zeros((0, 0))
+        if obs.ndim != 2:
+            raise ValueError("Proximity: obstacles must be [K, pd + 2]")
+        if len(obs) > PROXIMITY_MAX_OBSTACLES:
+            raise ValueError(f"Proximity: at most {PROXIMITY_MAX_OBSTACLES} obstacles")
+        if len(obs):
+            if obs.shape[1] < 3:
+                raise ValueError("Proximity: obstacles must be [K, pd + 2]")
+            if not np.all(np.isfinite(obs[:, :-2])):
+                raise ValueError("Proximity: obstacle centres must be finite")
+            self._check(obs[:, -2], obs[:, -1], "obstacle")
+        obs.setflags(write=False)  # the engine uploads the table once per device
+        self.obstacles = obs
+        if separation is None:
+            self.separation = None
+        else:
+            r, w = (float(v) for v in separation)
+            self._check(np.array([r]), np.array([w]), "separation")
+            self.separation = (r, w)
+
+    @staticmethod
+    def _check(r, w, what):
+        if not (np.all(np.isfinite(r)) and np.all(r > 0.0)):
+            raise ValueError(f"Proximity: {what} radii must be finite and > 0")
+        if not (np.all(np.isfinite(w)) and np.all(w >= 0.0)):
+            raise ValueError(f"Proximity: {what} weights must be finite and >= 0")
+
+    def check_pos_dim(self, pd):
+        """the obstacle table's columns against a fleet's position entries"""
+        if len(self.obstacles) and self.obstacles.shape[1] != pd + 2:
+            raise ValueError(f"Proximity: obstacles have {self.obstacles.shape[1]} columns, "
+                             f"a fleet with {pd} position entries needs {pd + 2}")
+
+    def table(self, pd):
+        """the obstacle rows [K, pd + 2] (K may be 0)"""
+        return self.obstacles.reshape(-1, pd + 2)
+
+    def sep(self):
+        """(radius, weight), (1.0, 0.0) for no separation term"""
+        return self.separation if self.separation is not None else (1.0, 0.0)
+
+
 class Fleet:
     """``count`` copies of one built-in system ``base`` (a DeviceDynamics, a system id 0..4
     or a name) as one device system (include/hop_fleet.h, csrc/fleet.hip): x = [x^0 | x^1 |
@@ -281,9 +351,15 @@ class Fleet:
     <= 16.  The engine and solver functions take the object itself as ``system`` / ``F``; it
     steps with the member's own dt unless ``dt`` is given.  ``wrap_idx`` holds the members'
     angle indices, repeated per member.  Calling it evaluates a NumPy twin of F on the host
-    (one state, or stacked rows), so ``host()`` wraps the same fleet for comparison."""
+    (one state, or stacked rows), so ``host()`` wraps the same fleet for comparison.
 
-    def __init__(self, base, count, dt=None):
+    ``proximity`` (a :class:`Proximity`) adds obstacle and member-separation bumps on the
+    members' ``pos_dim`` position entries as a stage cost evaluated on the device
+    (include/hop_fleet_proximity.h): engine.cost_true, engine.forward_linesearch and the
+    solver functions then run the proximity entries, and ``stage_cost()`` is its NumPy
+    twin."""
+
+    def __init__(self, base, count, dt=None, proximity=None):
         if isinstance(base, DeviceDynamics):
             sid, base_dt = int(base.system_id), float(base.dt)
         else:
@@ -308,6 +384,52 @@ class Fleet:
         self.wrap_idx = [a * ns + i for a in range(count) for i in wrap]
         self.position_idx = [a * ns + i for a in range(count) for i in pos]
         self._f_np = f_np
+        self.pos_dim = len(pos)
+        if proximity is not None:
+            if not isinstance(proximity, Proximity):
+                raise TypeError("Fleet: proximity must be a systems.Proximity")
+            proximity.check_pos_dim(self.pos_dim)
+        self.proximity = proximity
+
+    def stage_cost(self):
+        """The proximity cost as a NumPy callable (x, u) -> (c, cx [n], cxx [n, n]): what
+        ``host()`` users pass as ``extra_stage_cost``, and the twin the device kernels are
+        tested against.  Zeros for a fleet without a proximity cost."""
+        n, ns, pd, count = self.n, self.n_member, self.pos_dim, self.count
+        prox = self.proximity
+        rows = np.zeros((0, pd + 2)) if prox is None else prox.table(pd)
+        r_s, w_s = (1.0, 0.0) if prox is None else prox.sep()
+
+        def cost(x, u=None):
+            p = np.asarray(x, dtype=float).reshape(count, ns)[:, :pd]
+            c, cx, cxx = 0.0, np.zeros(n), np.zeros((n, n))
+
+            def add(a, b, d, r, w):  # one bump between member a and an obstacle or member b
+                nonlocal c
+                ci = w * np.exp(-float(d @ d) / (2.0 * r * r))
+                g, H = -(ci / (r * r)) * d, ci * np.outer(d, d) / r ** 4
+                sa = slice(a * ns, a * ns + pd)
+                c += ci
+                cx[sa] += g
+                cxx[sa, sa] += H
+                if b is not None:
+                    sb = slice(b * ns, b * ns + pd)
+                    cx[sb] -= g
+                    cxx[sb, sb] += H
+                    cxx[sa, sb] -= H
+                    cxx[sb, sa] -= H
+
+            for a in range(count):
+                for row in rows:
+                    if row[pd + 1] != 0.0:
+                        add(a, None, p[a] - row[:pd], row[pd], row[pd + 1])
+                if w_s != 0.0:
+                    for b in range(a + 1, count):
+                        add(a, b, p[a] - p[b], r_s, w_s)
+            return c, cx, cxx
+
+        cost.proximity = prox
+        return cost
 
     def fleet_params(self):
         """(system, count, dt): what the hop_fleet_* entries take."""
@@ -370,6 +492,48 @@ def make_fleet(base, count, N=None, seed=0, coupling=0.5, w_scale=1.0, T_min=Non
     Qf_m = alpha * np.eye(ns) if np.ndim(alpha) == 0 else np.asarray(alpha, dtype=float)
     return (F, x0, np.tile(np.asarray(xgm, dtype=float), F.count),
             np.tile(np.atleast_1d(np.asarray(urm, dtype=float)), F.count), Q,
+            _blockdiag(Rm, F.count), _blockdiag(Qf_m, F.count), float(w) * float(w_scale), int(Nn),
+            int(t_min if T_min is None else T_min), int(min(t_max, Nn - 5)), list(F.wrap_idx),
+            None)
+
+
+CROSSING_RADIUS, CROSSING_JITTER, CROSSING_TURN = 2.0, 0.15, 2.2
+CROSSING_OBSTACLE, CROSSING_OBS_RADIUS, CROSSING_SEP_RADIUS = (0.3, 0.2, 0.0), 0.5, 0.4
+
+
+def make_fleet_crossing(base, count, N=None, seed=0, w_scale=1.0, q_pos=0.5, bump_weight=1.5,
+                        T_min=None):
+    """A crossing problem of ``count`` members with a proximity cost
+    (tests/golden/make_golden_fleet_proximity.py's): the member maker's data as in
+    :func:`make_fleet`, without the coupling.  The starts' position entries lie on a circle
+    of radius 2 (its first ``pd`` coordinates), member a at angle 2 pi a / count + 0.15
+    N(0, 1) from ``seed``; the goals are the starts turned by 2.2 rad, so the members cross
+    near the centre.  Q gets ``q_pos`` added on the position entries (the select needs
+    weight there, see :class:`Proximity`).  One obstacle sits at (0.3, 0.2[, 0]) with radius
+    0.5, the separation radius is 0.4, and both bumps weigh ``bump_weight``.  Returns the
+    usual 13-tuple with F a :class:`Fleet` that carries the :class:`Proximity`."""
+    F0 = Fleet(base, 1)
+    sid, pd = F0.base_id, F0.pos_dim
+    mk = _MEMBER_MAKERS[sid]() if N is None else _MEMBER_MAKERS[sid](N=int(N))
+    Fm, x0m, xgm, urm, Qm, Rm, alpha, w, Nn, t_min, t_max = mk[:11]
+    prox = Proximity(
+        obstacles=[list(CROSSING_OBSTACLE[:pd]) + [CROSSING_OBS_RADIUS, float(bump_weight)]],
+        separation=(CROSSING_SEP_RADIUS, float(bump_weight)))
+    F = Fleet(Fm, count, proximity=prox)
+    ns = F.n_member
+    rng = np.random.default_rng(seed)
+    ang = 2.0 * np.pi * np.arange(F.count) / F.count \
+        + CROSSING_JITTER * rng.standard_normal(F.count)
+    x0 = np.tile(np.asarray(x0m, dtype=float), F.count)
+    xg = np.tile(np.asarray(xgm, dtype=float), F.count)
+    for a in range(F.count):
+        for ang_a, x in ((ang[a], x0), (ang[a] + CROSSING_TURN, xg)):
+            circle = CROSSING_RADIUS * np.array([np.cos(ang_a), np.sin(ang_a), 0.0])
+            x[a * ns:a * ns + pd] = circle[:pd]
+    Q = _blockdiag(Qm, F.count)
+    Q[F.position_idx, F.position_idx] += float(q_pos)
+    Qf_m = alpha * np.eye(ns) if np.ndim(alpha) == 0 else np.asarray(alpha, dtype=float)
+    return (F, x0, xg, np.tile(np.atleast_1d(np.asarray(urm, dtype=float)), F.count), Q,
             _blockdiag(Rm, F.count), _blockdiag(Qf_m, F.count), float(w) * float(w_scale), int(Nn),
             int(t_min if T_min is None else T_min), int(min(t_max, Nn - 5)), list(F.wrap_idx),
             None)
