@@ -174,6 +174,12 @@ FLEET_PROXIMITY_SIGNATURES = {
 }
 FLEET_MAX_OBSTACLES = 16  # include/hop_fleet_proximity.h HOP_FLEET_MAX_OBSTACLES
 
+# include/hop_team.h (teams: mixed fleets of the built-in systems); bound beside the others.
+# Every entry starts with a pointer to TeamParams; the rest is the fleet entry's list
+TEAM_SIGNATURES = {"hop_team_" + name[len("hop_fleet_"):]: sig
+                   for name, sig in FLEET_SIGNATURES.items()}
+TEAM_MAX_MEMBERS = 15  # include/hop_team.h HOP_TEAM_MAX_MEMBERS
+
 # include/hop_onepass.h (the one-pass window method's primitives); bound beside the others
 ONEPASS_SIGNATURES = {
     # system X U cost T_min T_max batch N J T_bar stream
@@ -216,6 +222,11 @@ class FleetParams(C.Structure):
     _fields_ = [("system", _I32), ("count", _I32), ("dt", C.c_double)]
 
 
+class TeamParams(C.Structure):
+    """hop_team_params (include/hop_team.h)."""
+    _fields_ = [("count", _I32), ("system", _I32 * TEAM_MAX_MEMBERS), ("dt", C.c_double)]
+
+
 class FleetProximity(C.Structure):
     """hop_fleet_proximity (include/hop_fleet_proximity.h)."""
     _fields_ = [("obstacles", _P), ("n_obs", _I32), ("sep_radius", C.c_double),
@@ -252,6 +263,7 @@ def load(path: str | None = None):
                                   + list(CHAIN_SIGNATURES.items())
                                   + list(FLEET_SIGNATURES.items())
                                   + list(FLEET_PROXIMITY_SIGNATURES.items())
+                                  + list(TEAM_SIGNATURES.items())
                                   + list(ONEPASS_SIGNATURES.items())
                                   + list(TESTHOOK_SIGNATURES.items())):
             if other and not hasattr(lib, name):

@@ -17,7 +17,7 @@ REPO = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libhop_amd.so")
 SOURCES = ["capi.hip", "augment.hip", "lft_sweep.hip", "lft_sweep_v2.hip", "lft_small.hip",
            "riccati.hip", "riccati_fast.hip", "linearize.hip", "forward.hip", "lft_wide.hip",
-           "riccati_wide.hip", "chain.hip", "onepass.hip", "lds_probe.hip", "fleet.hip"]
+           "riccati_wide.hip", "chain.hip", "onepass.hip", "lds_probe.hip", "fleet.hip", "team.hip"]
 # developer builds (HOP_DEV_BUILD=1 or --dev): the A/B schedules and stamped
 # instantiations, selected at run time by hop_set_options' variant number;
 # product builds compile none of them
@@ -28,7 +28,7 @@ if DEV:  # a separate library (load it with HOP_LIB=<path>): the product .so sta
 EXTRA = {}
 HEADERS = ["hop_device.hpp", "hop_kernels.hpp", "dpp_blocks.inc", "small_math.hpp", "wrap.hpp", "dynamics.hpp",
            "lu_pivot.hpp", "hop_wide_device.hpp", "chain_dynamics.hpp", "cost_device.hpp",
-           "onepass_pick.hpp", "fleet_math.hpp", "row_system.hpp", "fleet_proximity.hpp"]
+           "onepass_pick.hpp", "fleet_math.hpp", "row_system.hpp", "fleet_proximity.hpp", "team_math.hpp"]
 ARCH = os.environ.get("HOP_OFFLOAD_ARCH", "gfx950")
 # device code from its assembly, minus the DPP hazard pads the compiled code does not
 # need (tools/nop_elide.py); HOP_NO_ELIDE=1 compiles the plain way (hipcc -c)
@@ -58,7 +58,7 @@ def _digest():
         with open(os.path.join(CSRC, name), "rb") as f:
             h.update(f.read())
     for name in ("hop.h", "hop_wide.h", "hop_wide_jcurve.h", "hop_chain.h", "hop_onepass.h",
-                 "hop_testhooks.h", "hop_fleet.h", "hop_fleet_proximity.h"):
+                 "hop_testhooks.h", "hop_fleet.h", "hop_fleet_proximity.h", "hop_team.h"):
         with open(os.path.join(REPO, "include", name), "rb") as f:
             h.update(f.read())
     if ELIDE:  # the device code is what tools/nop_elide.py leaves of the compiler's

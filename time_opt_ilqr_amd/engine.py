@@ -826,9 +826,16 @@ def is_fleet(system) -> bool:
     return getattr(system, "fleet_params", None) is not None
 
 
+def is_team(system) -> bool:
+    """True for a systems.Team: members of different built-in systems stacked member-major
+    (include/hop_team.h); taken wherever a fleet without a proximity cost is."""
+    return getattr(system, "team_params", None) is not None
+
+
 def is_object_system(system) -> bool:
-    """a device system that is passed as the object itself: a spring chain or a fleet"""
-    return is_chain(system) or is_fleet(system)
+    """a device system that is passed as the object itself: a spring chain, a fleet or a
+    team"""
+    return is_chain(system) or is_fleet(system) or is_team(system)
 
 
 def _fleet_params(system):
@@ -836,9 +843,21 @@ def _fleet_params(system):
     return _lib.FleetParams(int(sid), int(count), float(dt))
 
 
+def _team_params(system):
+    ids, dt = system.team_params()
+    par = _lib.TeamParams()
+    par.count, par.dt = len(ids), float(dt)
+    for a, sid in enumerate(ids):
+        par.system[a] = int(sid)
+    return par
+
+
 def _object_entry(system, name):
-    """(hop_chain_<name> or hop_fleet_<name>, its parameter struct) of an object system"""
+    """(hop_chain_<name>, hop_fleet_<name> or hop_team_<name>, its parameter struct) of an
+    object system"""
     lib = _lib.load()
+    if is_team(system):
+        return getattr(lib, "hop_team_" + name), _team_params(system)
     if is_fleet(system):
         return getattr(lib, "hop_fleet_" + name), _fleet_params(system)
     return getattr(lib, "hop_chain_" + name), _chain_params(system)
@@ -898,10 +917,10 @@ def fleet_proximity_cost(fleet, X, want=("c", "cx", "cxx")):
 
 def _chain_cost_args(cost, Bn, n, m, dev, system=None):
     """hop_chain.h's cost arguments (xg bs u_ref bs Q R Qf w bs) of a CostParams; for a
-    fleet hop_fleet.h's, which end in the wrap mask."""
+    fleet hop_fleet.h's and for a team hop_team.h's, which end in the wrap mask."""
     torch = _torch()
-    fleet = is_fleet(system)
-    what = "fleet" if fleet else "spring chain"
+    fleet = is_fleet(system) or is_team(system)
+    what = "team" if is_team(system) else "fleet" if fleet else "spring chain"
     if cost.obstacles is not None and len(cost.obstacles):
         raise ValueError(f"a {what} takes no obstacle table")
     if not fleet and cost.wrap_idx is not None and len(cost.wrap_idx):
@@ -929,7 +948,8 @@ def _chain_cost_args(cost, Bn, n, m, dev, system=None):
 
 
 def system_dims(system) -> tuple:
-    """(n, m) of a system id or name (hop_system_dims), of a spring chain or of a fleet."""
+    """(n, m) of a system id or name (hop_system_dims), of a spring chain, a fleet or a
+    team."""
     if is_object_system(system):
         return int(system.n), int(system.m)
     sid = system_id(system)
@@ -1309,6 +1329,9 @@ def _onepass_system(system):
     if is_fleet(system):
         raise NotImplementedError("the one-pass primitives cover the five built-in device "
                                   "systems (n <= 12), not a fleet of them")
+    if is_team(system):
+        raise NotImplementedError("the one-pass primitives cover the five built-in device "
+                                  "systems (n <= 12), not a team of them")
     return system_id(system)
 
 

@@ -8,8 +8,8 @@ Same names, arguments and return shapes (lists of per-step NumPy blocks) for one
 trajectory; ``linearize_batch`` is the batched device form (torch tensors in
 HBM, the layout engine.propagate_traj / engine.riccati read).  ``F`` must be a
 :class:`~time_opt_ilqr_amd.systems.DeviceDynamics` or
-:class:`~time_opt_ilqr_amd.systems.SpringChain` or :class:`~time_opt_ilqr_amd.systems.Fleet`
-(a system the kernel knows):
+:class:`~time_opt_ilqr_amd.systems.SpringChain`, :class:`~time_opt_ilqr_amd.systems.Fleet`
+or :class:`~time_opt_ilqr_amd.systems.Team` (a system the kernel knows):
 an arbitrary Python callable is refused with TypeError rather than evaluated on
 the CPU.
 """
@@ -18,11 +18,11 @@ from __future__ import annotations
 import numpy as np
 
 from . import engine
-from .systems import DeviceDynamics, Fleet, SpringChain
+from .systems import DeviceDynamics, Fleet, SpringChain, Team
 
 
 def _check_F(F):
-    if not isinstance(F, (DeviceDynamics, SpringChain, Fleet)):
+    if not isinstance(F, (DeviceDynamics, SpringChain, Fleet, Team)):
         raise TypeError("F must be a time_opt_ilqr_amd.systems DeviceDynamics (the device "
                         "linearisation has no path for arbitrary Python dynamics)")
     return F

@@ -37,6 +37,9 @@ def check_scope(system, S_window, onepass_preimage, extra_stage_cost=None):
     if engine.is_fleet(system):
         raise NotImplementedError("method='onepass' is not implemented for a fleet (the "
                                   "one-pass primitives cover the five built-in systems)")
+    if engine.is_team(system):
+        raise NotImplementedError("method='onepass' is not implemented for a team (the "
+                                  "one-pass primitives cover the five built-in systems)")
     if isinstance(system, host_dynamics.HostDynamics) or (
             callable(system) and not hasattr(system, "system_id") and not engine.is_chain(system)):
         raise NotImplementedError("method='onepass' runs the five built-in device systems "

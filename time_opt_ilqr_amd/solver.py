@@ -135,12 +135,19 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
             raise NotImplementedError("a fleet takes no Python stage cost: give it a "
                                       "systems.Proximity, or wrap it in "
                                       "host_dynamics.HostDynamics")
+        if engine.is_team(system) and extra_stage_cost is not None:
+            raise NotImplementedError("a team takes no Python stage cost: wrap it in "
+                                      "host_dynamics.HostDynamics (Team.host())")
         if extra_stage_cost is not None:
             raise ValueError("device dynamics take the point-mass obstacles table; a "
                              "Python extra_stage_cost needs host dynamics")
         if engine.is_fleet(system):  # a systems.Fleet: the object is the system
             if obstacles is not None and len(obstacles) > 0:
                 raise NotImplementedError("a fleet takes no obstacle table")
+            sid, dt = system, float(system.dt)  # it steps with its own dt
+        elif engine.is_team(system):  # a systems.Team: the object is the system
+            if obstacles is not None and len(obstacles) > 0:
+                raise NotImplementedError("a team takes no obstacle table")
             sid, dt = system, float(system.dt)  # it steps with its own dt
         elif engine.is_chain(system):  # a systems.SpringChain: the object is the system
             if obstacles is not None and len(obstacles) > 0:
@@ -394,22 +401,22 @@ def _host_linesearch(system, Xh, Uh, T_star, K, k, active, cost_np, alphas, extr
 # ---------------------------------------------------------------------------
 
 def _dyn(F):
-    from .systems import DeviceDynamics, Fleet, SpringChain
-    if not isinstance(F, (DeviceDynamics, SpringChain, Fleet)):
-        raise TypeError("F must be a time_opt_ilqr_amd.systems.DeviceDynamics, SpringChain or "
-                        "Fleet (use the systems.make_* makers)")
+    from .systems import DeviceDynamics, Fleet, SpringChain, Team
+    if not isinstance(F, (DeviceDynamics, SpringChain, Fleet, Team)):
+        raise TypeError("F must be a time_opt_ilqr_amd.systems.DeviceDynamics, SpringChain, "
+                        "Fleet or Team (use the systems.make_* makers)")
     return F
 
 
 def _sys(F):
-    """what the engine takes as ``system``: a built-in system's id, a SpringChain or a
-    Fleet itself"""
+    """what the engine takes as ``system``: a built-in system's id, or a SpringChain, a
+    Fleet or a Team itself"""
     return F if engine.is_object_system(F) else F.system_id
 
 
 def _on_device(F) -> bool:
-    from .systems import DeviceDynamics, Fleet, SpringChain
-    if isinstance(F, (DeviceDynamics, SpringChain, Fleet)):
+    from .systems import DeviceDynamics, Fleet, SpringChain, Team
+    if isinstance(F, (DeviceDynamics, SpringChain, Fleet, Team)):
         return True
     if not callable(F):
         raise TypeError("F must be a systems.DeviceDynamics or a callable F(x, u) -> x_next")
@@ -564,6 +571,9 @@ def ilqr_timeopt(F, x0, xg, u_ref, Q, R, alpha, w, N: int, T_min: int, T_max: in
     n = x0.shape[1]
     if engine.is_fleet(F) and extra_stage_cost is not None:
         raise NotImplementedError("a fleet has no stage cost besides its dense Q and R "
+                                  "(wrap it in host_dynamics.HostDynamics for one)")
+    if engine.is_team(F) and extra_stage_cost is not None:
+        raise NotImplementedError("a team has no stage cost besides its dense Q and R "
                                   "(wrap it in host_dynamics.HostDynamics for one)")
     if _on_device(F) and _is_obstacle_cost(extra_stage_cost):
         F = _dyn(F)

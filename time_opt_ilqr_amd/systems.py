@@ -537,3 +537,145 @@ def make_fleet_crossing(base, count, N=None, seed=0, w_scale=1.0, q_pos=0.5, bum
             _blockdiag(Rm, F.count), _blockdiag(Qf_m, F.count), float(w) * float(w_scale), int(Nn),
             int(t_min if T_min is None else T_min), int(min(t_max, Nn - 5)), list(F.wrap_idx),
             None)
+
+
+# ---- teams: members of different built-in systems, coupled through the cost ---------
+
+TEAM_MAX_MEMBERS = 15  # include/hop_team.h HOP_TEAM_MAX_MEMBERS
+
+
+class Team:
+    """Members of different built-in systems as one device system (include/hop_team.h,
+    csrc/team.hip).  ``members`` is a sequence of DeviceDynamics, system ids 0..4 or names,
+    1 to 15 of them; member a owns states ``[x_offsets[a], x_offsets[a] + n_s(a))`` and
+    inputs ``[u_offsets[a], u_offsets[a] + m_s(a))``, the offsets being the running sums in
+    member order.  F is the concatenation of the members' F at one shared step ``dt``, the
+    members coupled only through dense Q, Qf and R; n = sum n_s <= 31 and m = sum m_s <= 16.
+    The shared step is ``dt`` if given, else the members' own, which must then agree
+    (cart-pole and segway default to 0.02, the others to 0.05).  The engine and solver
+    functions take the object itself as ``system`` / ``F``, wherever they take a
+    :class:`Fleet` without a proximity cost; a team of equal members computes that fleet's
+    numbers bit for bit.  ``wrap_idx`` and ``position_idx`` hold the members' angle and
+    position indices shifted by their offsets.  Calling it evaluates a NumPy twin of F on
+    the host (one state, or stacked rows), so ``host()`` wraps the same team for comparison.
+    A team takes no proximity cost: its members' positions differ in dimension."""
+
+    def __init__(self, members, dt=None):
+        try:
+            members = list(members)
+        except TypeError:
+            raise ValueError("Team: members must be a sequence of systems") from None
+        if not 1 <= len(members) <= TEAM_MAX_MEMBERS:
+            raise ValueError(f"Team needs 1 to {TEAM_MAX_MEMBERS} members, got {len(members)}")
+        ids, dts = [], []
+        for mem in members:
+            if isinstance(mem, DeviceDynamics):
+                sid, own = mem.system_id, float(mem.dt)
+            else:
+                try:
+                    sid = engine.system_id(mem)
+                except ValueError:
+                    raise ValueError(f"Team: unknown member {mem!r}") from None
+                own = None
+            if not isinstance(sid, (int, np.integer)) or int(sid) not in _MEMBERS:
+                raise ValueError(f"Team: unknown member {mem!r}")
+            sid = int(sid)
+            ids.append(sid)
+            dts.append(float(_MEMBER_MAKERS[sid]()[0].dt) if own is None else own)
+        self.member_ids = tuple(ids)
+        sizes = [_MEMBERS[s][:2] for s in ids]
+        self.n, self.m = sum(s[0] for s in sizes), sum(s[1] for s in sizes)
+        if self.n > FLEET_MAX_N or self.m > FLEET_MAX_M:
+            raise ValueError(f"Team: n = {self.n}, m = {self.m}; the limits are "
+                             f"n <= {FLEET_MAX_N} and m <= {FLEET_MAX_M}")
+        if dt is None:
+            if len(set(dts)) != 1:
+                raise ValueError(f"Team: the members' own steps differ ({sorted(set(dts))}): "
+                                 "give the shared dt")
+            self.dt = dts[0]
+        else:
+            self.dt = float(dt)
+        if not self.dt > 0.0:
+            raise ValueError("Team: dt must be positive")
+        self.x_offsets = tuple(int(v) for v in np.cumsum([0] + [s[0] for s in sizes[:-1]]))
+        self.u_offsets = tuple(int(v) for v in np.cumsum([0] + [s[1] for s in sizes[:-1]]))
+        self.wrap_idx = [xo + i for s, xo in zip(ids, self.x_offsets) for i in _MEMBERS[s][3]]
+        self.position_idx = [xo + i for s, xo in zip(ids, self.x_offsets)
+                             for i in _MEMBERS[s][4]]
+        self.name = "team_" + "+".join(_MEMBERS[s][2] for s in ids)
+
+    def team_params(self):
+        """(member system ids, dt): what the hop_team_* entries take."""
+        return self.member_ids, self.dt
+
+    def __call__(self, x, u):
+        """F on the host in NumPy: x [n], u [m] -> [n], or stacked rows [K, n], [K, m]."""
+        x = np.asarray(x, dtype=float)
+        u = np.asarray(u, dtype=float)
+        one = x.ndim == 1
+        xr, ur = x.reshape(-1, self.n), u.reshape(-1, self.m)
+        out = np.empty_like(xr)
+        for sid, xo, uo in zip(self.member_ids, self.x_offsets, self.u_offsets):
+            ns, ms, f_np = _MEMBERS[sid][0], _MEMBERS[sid][1], _MEMBERS[sid][5]
+            out[:, xo:xo + ns] = f_np(xr[:, xo:xo + ns], ur[:, uo:uo + ms], self.dt)
+        return out[0] if one else out
+
+    def batch(self, X, U):
+        """x' for device tensors X [..., n], U [..., m]."""
+        return engine.dynamics(self, X, U, self.dt)
+
+    def host(self):
+        """The same team as a host_dynamics.HostDynamics(vectorized=True)."""
+        from .host_dynamics import HostDynamics
+        return HostDynamics(self.__call__, self.n, self.m, name=self.name + "_host",
+                            vectorized=True)
+
+
+def _blocks(mats):
+    mats = [np.atleast_2d(np.asarray(M, dtype=float)) for M in mats]
+    out = np.zeros((sum(len(M) for M in mats),) * 2)
+    o = 0
+    for M in mats:
+        out[o:o + len(M), o:o + len(M)] = M
+        o += len(M)
+    return out
+
+
+def make_team(members, N=None, seed=0, coupling=0.5, w_scale=1.0, T_min=None, dt=None):
+    """A joint problem of mixed members (tests/golden/make_golden_team.py's): every
+    member's maker is called with the team's dt and N (N = the smallest of the makers' own
+    unless given).  x0 = the makers' starts plus FLEET_NOISE[kind] N(0, 1) from ``seed`` on
+    the position entries, drawn in member order, then entry order.  Q = the block diagonal
+    of the members' Q plus a path Laplacian over consecutive members' first coordinates
+    with, for members a and a + 1, kappa = coupling min(Q_a[0, 0], Q_a+1[0, 0]) (both taken
+    before any coupling is added), or coupling max(Q_a[0, 0], Q_a+1[0, 0], 1) where that
+    minimum is 0.  R and the terminal weight (returned expanded, [n, n]) are block diagonal,
+    w = w_scale times the largest of the makers', T_max = min(the makers', N - 5) and T_min
+    the largest of the makers' unless given.  Returns the usual 13-tuple with F a
+    :class:`Team`."""
+    F = Team(members, dt=dt)
+    if N is None:
+        N = min(int(_MEMBER_MAKERS[s]()[8]) for s in F.member_ids)
+    N = int(N)
+    mks = [_MEMBER_MAKERS[s](dt=F.dt, N=N) for s in F.member_ids]
+    rng = np.random.default_rng(seed)
+    x0 = np.concatenate([np.asarray(mk[1], dtype=float) for mk in mks])
+    for sid, xo in zip(F.member_ids, F.x_offsets):
+        pos = [xo + i for i in _MEMBERS[sid][4]]
+        x0[pos] += FLEET_NOISE[sid] * rng.standard_normal(len(pos))
+    Q = _blocks([mk[4] for mk in mks])
+    q00 = [float(np.asarray(mk[4], dtype=float)[0, 0]) for mk in mks]
+    for a in range(len(mks) - 1):
+        lo = min(q00[a], q00[a + 1])
+        kappa = float(coupling) * (lo if lo != 0.0 else max(q00[a], q00[a + 1], 1.0))
+        i, j = F.x_offsets[a], F.x_offsets[a + 1]
+        Q[i, i] += kappa
+        Q[j, j] += kappa
+        Q[i, j] -= kappa
+        Q[j, i] -= kappa
+    Qf = _blocks([mk[6] * np.eye(len(mk[1])) if np.ndim(mk[6]) == 0 else mk[6] for mk in mks])
+    return (F, x0, np.concatenate([np.asarray(mk[2], dtype=float) for mk in mks]),
+            np.concatenate([np.atleast_1d(np.asarray(mk[3], dtype=float)) for mk in mks]), Q,
+            _blocks([mk[5] for mk in mks]), Qf, float(w_scale) * max(float(mk[7]) for mk in mks),
+            N, int(max(int(mk[9]) for mk in mks) if T_min is None else T_min),
+            int(min(min(int(mk[10]) for mk in mks), N - 5)), list(F.wrap_idx), None)
