@@ -24,6 +24,26 @@
  *      HOP_ST_NONFINITE a non-finite value (reference: FloatingPointError)
  *      HOP_ST_FAIL      not PD after every try (reference: LinAlgError, or
  *                       backward_pass_truncated's ok=False)
+ *
+ * Memory contract (every entry of this header and of the headers that include it: the
+ * wide, chain, fleet, team and one-pass entries; tests/test_gpu_global_memory.py holds
+ * each of them to it)
+ *  - Alignment: a pointer needs the alignment of its element type and no more (8 bytes
+ *    for double, 4 for float and int32_t), whatever the shape: a view that starts at any
+ *    problem of a larger tensor is a valid argument.  A `void* workspace` is read as
+ *    doubles and needs 8 bytes; the one stricter requirement is the 256 bytes of
+ *    hop_lft_sweep_traj_*'s workspace, which the entry checks (HOP_E_ARG).
+ *  - Written extents: an entry writes the elements its comment lists as outputs and
+ *    nothing else -- not the steps past n_use, n_build or a problem's horizon, not the
+ *    padding between strided rows, not a nullable output that is NULL, and no byte
+ *    before or after a tensor.  Where an extent depends on the data it is stated with
+ *    the entry (hop_riccati_*: the horizon; hop_linearize_*: n_use).
+ *  - Inputs are never written.  The only in/out arguments are the state tensors of
+ *    hop_ilqr_accept_f64 (lm, T_bar, J_hist, T_hist, n_hist, done) and done / crashed
+ *    of hop_ilqr_select_mask.
+ *  - Results never depend on memory outside the tensors: the kernels prefetch the next
+ *    step's and the next problem's blocks at clamped or bounds-checked addresses, and
+ *    what such a load returns reaches no output and no status word.
  */
 #ifndef HOP_H
 #define HOP_H
@@ -385,6 +405,10 @@ int hop_lft_sweep_traj_f32(const float* A, const float* Bm, const float* a_res, 
  *   Outputs: K [batch][n_alloc][m][n], k [batch][n_alloc][m];
  *      nullable Vxx [batch][n_alloc+1][n][n], Vx [batch][n_alloc+1][n],
  *      V0 [batch][n_alloc+1]; status [batch] (HOP_ST_FAIL = ok=False / raise).
+ *      Written (both modes, a problem that does not fail): K and k at steps
+ *      < horizon[b]; Vxx, Vx and V0, where given, at steps <= horizon[b]; status [b].
+ *      The steps after them are left as they were (the reference returns lists of that
+ *      length).
  */
 int hop_riccati_f64(const double* A, const double* Bm, const double* X, const double* U,
                     const double* xg, int64_t xg_batch_stride, const double* u_ref,
@@ -508,6 +532,7 @@ int hop_system_dims(int32_t system, int32_t* n, int32_t* m);
  *   Fx    [batch][n_alloc][n] = F(x_k, u_k)          (nullable)
  *   h = max(eps, rel * max(1, |v|)) per entry (reference defaults 1e-5 / 1e-6);
  *   forward differences give an all-NaN (A_k, B_k) when F(x_k, u_k) is not finite.
+ *   A, Bm, a_res and Fx are written at steps k < n_use only.
  */
 int hop_linearize_f64(int32_t system, double dt, const double* X, const double* U,
                       int64_t batch, int32_t n_alloc, int32_t n_use, int32_t central,
@@ -589,7 +614,11 @@ int hop_cost_true_f64(int32_t system, const double* X, const double* U, const in
  *   active [batch] nullable (0 = skip: X' = X, U' = U, accepted = -2).
  *   Out: X_new [batch][N+1][n], U_new [batch][N][m], J [batch] (the accepted J'
  *   or J_old), J_old [batch], accepted [batch] = index of the accepted alpha or -1.
- *   workspace: hop_forward_workspace_bytes(system, batch, N, n_alpha) bytes.
+ *   Every output is written whole for every problem: the rows of X_new and U_new past
+ *   T_star are the accepted rollout's (it runs all N steps), and a problem that is
+ *   inactive or accepts nothing gets copies of X and U.
+ *   workspace: hop_forward_workspace_bytes(system, batch, N, n_alpha) bytes, 8-byte
+ *   aligned (candidate costs and rollouts, doubles).
  */
 size_t hop_forward_workspace_bytes(int32_t system, int64_t batch, int32_t N, int32_t n_alpha);
 int hop_forward_linesearch_f64(int32_t system, double dt, const double* X, const double* U,

@@ -15,7 +15,8 @@
  *   Evaluated in that order without FMA contraction: sin is the only operation that can
  *   differ from NumPy, and the q' half of F is bit-identical to it.
  *
- * Layout conventions, error codes, streams and hop_last_error are those of hop.h.
+ * Layout conventions, the memory contract (element alignment, written extents, inputs
+ * never written), error codes, streams and hop_last_error are those of hop.h.
  * Every entry validates its arguments on the host before any launch:
  *   HOP_E_SIZE (-2)  p outside [1, HOP_CHAIN_MAX_P] or m outside [1, p]
  *   HOP_E_ARG  (-1)  null pointers, n_use > n_alloc, n_alpha outside [1, 8], dt <= 0,

@@ -12,7 +12,8 @@
  *   evaluated by the member's own arithmetic (hop_dynamics_f64's): one fleet step is
  *   bit for bit the members' steps.  Q and Qf are dense n x n, R is dense m x m.
  *
- * Layout conventions, error codes, streams and hop_last_error are those of hop.h.
+ * Layout conventions, the memory contract (element alignment, written extents, inputs
+ * never written), error codes, streams and hop_last_error are those of hop.h.
  * Every entry validates its arguments on the host before any launch:
  *   HOP_E_SIZE (-2)  count < 1, n > HOP_FLEET_MAX_N or m > HOP_FLEET_MAX_M
  *   HOP_E_ARG  (-1)  an unknown system, null pointers, n_use > n_alloc, n_alpha outside

@@ -22,7 +22,8 @@
  *   The LFT select inverts Q_k + cxx: a Q that is zero on the position entries makes it
  *   degenerate once a rank-one cxx is added, so give the positions weight.
  *
- * Layout conventions, error codes, streams and hop_last_error are those of hop_fleet.h.
+ * Layout conventions, the memory contract of hop.h, error codes, streams and
+ * hop_last_error are those of hop_fleet.h.
  * Every entry validates its arguments on the host before any launch; besides the codes of
  * hop_fleet.h:
  *   HOP_E_ARG (-1)  a null `prox`, n_obs outside [0, HOP_FLEET_MAX_OBSTACLES], a null table

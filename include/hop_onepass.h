@@ -6,7 +6,8 @@
  * extended trajectory.  hop.h, hop_wide.h, hop_wide_jcurve.h and hop_chain.h keep their
  * entries; nothing here changes them, and the ABI version of hop.h covers this header too.
  *
- * Layout conventions, error codes, streams and hop_last_error are those of hop.h; the
+ * Layout conventions, the memory contract (every output below is written whole; the byte
+ * workspace is 8-byte aligned), error codes, streams and hop_last_error are those of hop.h; the
  * cost arguments (xg .. wrap_mask) are hop_cost_true_f64's, in its order.  fp64 only.
  * Every entry validates its arguments on the host before any launch:
  *   HOP_E_ARG  (-1)  unknown system, null pointers, negative sizes or strides, windows or

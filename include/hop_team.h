@@ -16,7 +16,8 @@
  *   dense m x m.  A team of `count` members of one kind is hop_fleet.h's fleet of them,
  *   bit for bit on every output.
  *
- * Layout conventions, error codes, streams and hop_last_error are those of hop.h.
+ * Layout conventions, the memory contract (element alignment, written extents, inputs
+ * never written), error codes, streams and hop_last_error are those of hop.h.
  * Every entry validates its arguments on the host before any launch:
  *   HOP_E_SIZE (-2)  count outside [1, HOP_TEAM_MAX_MEMBERS], n > HOP_FLEET_MAX_N or
  *                    m > HOP_FLEET_MAX_M

@@ -4,7 +4,7 @@
  * (HOP_MAX_DIM) and their kernels, hop_wide.h keeps its three entries; nothing here
  * changes them, and the ABI version of hop.h covers this header too.
  *
- * Layout conventions, status bits, error codes, streams and hop_last_error are those
+ * Layout conventions, the memory contract, status bits, error codes, streams and hop_last_error are those
  * of hop.h.  The entry validates its arguments on the host before any launch.
  */
 #ifndef HOP_WIDE_JCURVE_H
