@@ -180,6 +180,19 @@ TEAM_SIGNATURES = {"hop_team_" + name[len("hop_fleet_"):]: sig
                    for name, sig in FLEET_SIGNATURES.items()}
 TEAM_MAX_MEMBERS = 15  # include/hop_team.h HOP_TEAM_MAX_MEMBERS
 
+# include/hop_mixed_proximity.h (the teams' proximity cost); bound beside the others.  The
+# composition is passed flat (members, system [members]; the line search also takes dt), the
+# rest is the fleet proximity entry's list after its parameter pointer
+MIXED_PROXIMITY_SIGNATURES = {
+    # members system prox X x_stride count c cx cxx stream
+    "hop_mixed_proximity_taylor_f64": (C.c_int, [_I32, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "hop_mixed_prox_cost_true_f64": (C.c_int, [_I32, _P, _P, _P, _P] + _FCOST + [_P] +
+                                     [_I64, _I32, _P, _P]),
+    "hop_mixed_prox_forward_linesearch_f64": (C.c_int, [_I32, _P, C.c_double, _P, _P] + _FCOST +
+                                              [_P] + [_P, _P, _P, _P, _P, _I32, _I64, _I32, _P,
+                                                      C.c_size_t, _P, _P, _P, _P, _P, _P]),
+}
+
 # include/hop_onepass.h (the one-pass window method's primitives); bound beside the others
 ONEPASS_SIGNATURES = {
     # system X U cost T_min T_max batch N J T_bar stream
@@ -264,6 +277,7 @@ def load(path: str | None = None):
                                   + list(FLEET_SIGNATURES.items())
                                   + list(FLEET_PROXIMITY_SIGNATURES.items())
                                   + list(TEAM_SIGNATURES.items())
+                                  + list(MIXED_PROXIMITY_SIGNATURES.items())
                                   + list(ONEPASS_SIGNATURES.items())
                                   + list(TESTHOOK_SIGNATURES.items())):
             if other and not hasattr(lib, name):

@@ -28,7 +28,8 @@ if DEV:  # a separate library (load it with HOP_LIB=<path>): the product .so sta
 EXTRA = {}
 HEADERS = ["hop_device.hpp", "hop_kernels.hpp", "dpp_blocks.inc", "small_math.hpp", "wrap.hpp", "dynamics.hpp",
            "lu_pivot.hpp", "hop_wide_device.hpp", "chain_dynamics.hpp", "cost_device.hpp",
-           "onepass_pick.hpp", "fleet_math.hpp", "row_system.hpp", "fleet_proximity.hpp", "team_math.hpp"]
+           "onepass_pick.hpp", "fleet_math.hpp", "row_system.hpp", "fleet_proximity.hpp", "team_math.hpp",
+           "team_proximity.hpp"]
 ARCH = os.environ.get("HOP_OFFLOAD_ARCH", "gfx950")
 # device code from its assembly, minus the DPP hazard pads the compiled code does not
 # need (tools/nop_elide.py); HOP_NO_ELIDE=1 compiles the plain way (hipcc -c)
@@ -58,7 +59,8 @@ def _digest():
         with open(os.path.join(CSRC, name), "rb") as f:
             h.update(f.read())
     for name in ("hop.h", "hop_wide.h", "hop_wide_jcurve.h", "hop_chain.h", "hop_onepass.h",
-                 "hop_testhooks.h", "hop_fleet.h", "hop_fleet_proximity.h", "hop_team.h"):
+                 "hop_testhooks.h", "hop_fleet.h", "hop_fleet_proximity.h", "hop_team.h",
+                 "hop_mixed_proximity.h"):
         with open(os.path.join(REPO, "include", name), "rb") as f:
             h.update(f.read())
     if ELIDE:  # the device code is what tools/nop_elide.py leaves of the compiler's

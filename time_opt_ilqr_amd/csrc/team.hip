@@ -28,6 +28,9 @@
 // Linearisation: lane a evaluates member a's base point and finite-difference columns
 // (team_math.hpp, linearize.hip's arithmetic) and writes rows [xo_a, xo_a + n_s) of A_k
 // and B_k in full, the off-block entries by the reference's rule.
+//
+// The proximity cost (include/hop_mixed_proximity.h) is team_proximity.hpp, included below:
+// TeamProxRow<NSMAX, MSMAX>, the policy with the cost in stage_inc, and the Taylor kernel.
 #include "row_system.hpp"
 #include "team_math.hpp"
 #include "../../include/hop_team.h"
@@ -386,9 +389,16 @@ int with_team(const hop_team_params* q, F&& f) {
 }  // namespace team
 }  // namespace hop
 
+// the proximity cost: TeamProxRow<NSMAX, MSMAX> and the Taylor kernel
+// (hop_mixed_proximity.h)
+#include "../../include/hop_mixed_proximity.h"
+#include "team_proximity.hpp"
+
 // ---------------------------------------------------------------- C entries
 namespace rowsys = hop::rowsys;
 using hop::team::Par;
+using hop::team::ProxPar;
+using hop::team::with_mixed_prox;
 using hop::team::with_team;
 
 extern "C" {
@@ -458,6 +468,47 @@ int hop_team_forward_linesearch_f64(const hop_team_params* params, const double*
   const rowsys::CostC cost{xg, xg_batch_stride, u_ref, u_ref_batch_stride, Q, R, Qf, w,
                            w_batch_stride, wrap_mask};
   return with_team(params, [&](auto s, const Par& P) {
+    return rowsys::linesearch_entry<decltype(s)>(P, X, U, cost, T_star, active, K, k, alphas,
+                                                 n_alpha, batch, N, workspace, workspace_bytes,
+                                                 X_new, U_new, J, J_old, accepted, stream);
+  });
+}
+
+// ---- include/hop_mixed_proximity.h
+int hop_mixed_proximity_taylor_f64(int32_t members, const int32_t* system,
+                                   const hop_fleet_proximity* prox, const double* X,
+                                   int64_t x_stride, int64_t count, double* c, double* cx,
+                                   double* cxx, void* stream) {
+  return with_mixed_prox(members, system, false, 0.0, prox, [&](auto, const ProxPar& P) {
+    return hop::team::taylor_entry(P, X, x_stride, count, c, cx, cxx, stream);
+  });
+}
+
+int hop_mixed_prox_cost_true_f64(int32_t members, const int32_t* system, const double* X,
+                                 const double* U, const int32_t* T_star, const double* xg,
+                                 int64_t xg_batch_stride, const double* u_ref,
+                                 int64_t u_ref_batch_stride, const double* Q, const double* R,
+                                 const double* Qf, const double* w, int64_t w_batch_stride,
+                                 uint32_t wrap_mask, const hop_fleet_proximity* prox,
+                                 int64_t batch, int32_t N, double* J, void* stream) {
+  const rowsys::CostC cost{xg, xg_batch_stride, u_ref, u_ref_batch_stride, Q, R, Qf, w,
+                           w_batch_stride, wrap_mask};
+  return with_mixed_prox(members, system, false, 0.0, prox, [&](auto s, const ProxPar& P) {
+    return rowsys::cost_entry<decltype(s)>(P, X, U, T_star, cost, batch, N, J, stream);
+  });
+}
+
+int hop_mixed_prox_forward_linesearch_f64(
+    int32_t members, const int32_t* system, double dt, const double* X, const double* U,
+    const double* xg, int64_t xg_batch_stride, const double* u_ref, int64_t u_ref_batch_stride,
+    const double* Q, const double* R, const double* Qf, const double* w, int64_t w_batch_stride,
+    uint32_t wrap_mask, const hop_fleet_proximity* prox, const int32_t* T_star,
+    const int32_t* active, const double* K, const double* k, const double* alphas,
+    int32_t n_alpha, int64_t batch, int32_t N, void* workspace, size_t workspace_bytes,
+    double* X_new, double* U_new, double* J, double* J_old, int32_t* accepted, void* stream) {
+  const rowsys::CostC cost{xg, xg_batch_stride, u_ref, u_ref_batch_stride, Q, R, Qf, w,
+                           w_batch_stride, wrap_mask};
+  return with_mixed_prox(members, system, true, dt, prox, [&](auto s, const ProxPar& P) {
     return rowsys::linesearch_entry<decltype(s)>(P, X, U, cost, T_star, active, K, k, alphas,
                                                  n_alpha, batch, N, workspace, workspace_bytes,
                                                  X_new, U_new, J, J_old, accepted, stream);

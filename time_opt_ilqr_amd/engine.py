@@ -828,7 +828,8 @@ def is_fleet(system) -> bool:
 
 def is_team(system) -> bool:
     """True for a systems.Team: members of different built-in systems stacked member-major
-    (include/hop_team.h); taken wherever a fleet without a proximity cost is."""
+    (include/hop_team.h); taken wherever a fleet is.  One that carries a proximity cost
+    (Team.with_proximity) runs the entries of include/hop_mixed_proximity.h."""
     return getattr(system, "team_params", None) is not None
 
 
@@ -869,9 +870,9 @@ def fleet_proximity(system):
 
 
 def _proximity_struct(system, dev):
-    """(hop_fleet_proximity of a fleet's cost, the device table it points to)"""
+    """(hop_fleet_proximity of a fleet's or a team's cost, the device table it points to)"""
     torch = _torch()
-    prox = fleet_proximity(system)
+    prox = team_proximity(system) if is_team(system) else fleet_proximity(system)
     rows = prox.table(int(system.pos_dim))
     tab = None
     if len(rows):  # uploaded once per device and kept on the Proximity
@@ -909,6 +910,48 @@ def fleet_proximity_cost(fleet, X, want=("c", "cx", "cxx")):
     fp = _fleet_params(fleet)
     rc = _lib.load().hop_fleet_proximity_taylor_f64(
         _lib.C.byref(fp), _lib.C.byref(par), _lib.ptr(rows), n, rows.shape[0], _lib.ptr(c),
+        _lib.ptr(cx), _lib.ptr(cxx), _lib.stream_handle(dev))
+    _lib.check(rc)
+    del tab
+    return c, cx, cxx
+
+
+def team_proximity(system):
+    """the systems.Proximity of a team that carries one (Team.with_proximity), else None"""
+    return getattr(system, "proximity", None) if is_team(system) else None
+
+
+def _team_members(system):
+    """(members, system ids as a host int32 array): the flat composition that the
+    hop_mixed_* entries take"""
+    ids = system.team_params()[0]
+    return len(ids), (_lib.C.c_int32 * len(ids))(*(int(s) for s in ids))
+
+
+def team_proximity_cost(team, X, want=("c", "cx", "cxx")):
+    """A team's proximity cost (systems.Proximity, include/hop_mixed_proximity.h) and its
+    second-order Taylor terms at every state row of X [..., n]: returns (c [...],
+    cx [..., n], cxx [..., n, n]) (entries not in `want` are None), the team's counterpart
+    of fleet_proximity_cost.  The members' positions are padded with zeros to the team's
+    ``pos_dim``; cx and cxx are restricted to the coordinates each member has."""
+    torch = _torch()
+    if team_proximity(team) is None:
+        raise ValueError("team_proximity_cost needs a systems.Team with a proximity cost "
+                         "(Team.with_proximity)")
+    X = _dev(X, "X", torch.float64)
+    dev = X.device
+    n = int(team.n)
+    if X.shape[-1] != n:
+        raise ValueError(f"X must end in {n}")
+    rows = X.reshape(-1, n)
+    lead = tuple(X.shape[:-1])
+    c = torch.empty(lead, dtype=torch.float64, device=dev) if "c" in want else None
+    cx = torch.empty(lead + (n,), dtype=torch.float64, device=dev) if "cx" in want else None
+    cxx = torch.empty(lead + (n, n), dtype=torch.float64, device=dev) if "cxx" in want else None
+    par, tab = _proximity_struct(team, dev)
+    members, ids = _team_members(team)
+    rc = _lib.load().hop_mixed_proximity_taylor_f64(
+        members, ids, _lib.C.byref(par), _lib.ptr(rows), n, rows.shape[0], _lib.ptr(c),
         _lib.ptr(cx), _lib.ptr(cxx), _lib.stream_handle(dev))
     _lib.check(rc)
     del tab
@@ -1188,6 +1231,13 @@ def cost_true(system, X, U, T_star, cost: CostParams):
         rc = _lib.load().hop_fleet_prox_cost_true_f64(
             _lib.C.byref(_fleet_params(sid)), _lib.ptr(X), _lib.ptr(U), _lib.ptr(T), *cargs,
             _lib.C.byref(px), Bn, N, _lib.ptr(J), _lib.stream_handle(dev))
+    elif team_proximity(sid) is not None:  # the team's entry with the proximity cost
+        cargs, keep = _chain_cost_args(cost, Bn, n, m, dev, sid)
+        px, tab = _proximity_struct(sid, dev)
+        keep += (tab,)
+        rc = _lib.load().hop_mixed_prox_cost_true_f64(
+            *_team_members(sid), _lib.ptr(X), _lib.ptr(U), _lib.ptr(T), *cargs,
+            _lib.C.byref(px), Bn, N, _lib.ptr(J), _lib.stream_handle(dev))
     elif is_object_system(sid):
         cargs, keep = _chain_cost_args(cost, Bn, n, m, dev, sid)
         fn, par = _object_entry(sid, "cost_true_f64")
@@ -1253,6 +1303,12 @@ def forward_linesearch(system, X, U, T_star, K, k, cost: CostParams, dt: float, 
         keep += (tab,)
         cargs = cargs + [_lib.C.byref(px)]
         fn = lib.hop_fleet_prox_forward_linesearch_f64
+    elif team_proximity(sid) is not None:  # the team's entry with the proximity cost
+        px, tab = _proximity_struct(sid, dev)
+        keep += (tab,)
+        cargs = cargs + [_lib.C.byref(px)]
+        head = _team_members(sid) + (float(sid.dt),)
+        fn = lib.hop_mixed_prox_forward_linesearch_f64
     rc = fn(*head, _lib.ptr(X), _lib.ptr(U), *cargs, _lib.ptr(T), _lib.ptr(act),
             _lib.ptr(K), _lib.ptr(k), c_al, len(al), Bn, N, _lib.C.c_void_p(ws.data_ptr()),
             ws_bytes, _lib.ptr(out.X), _lib.ptr(out.U), _lib.ptr(out.J), _lib.ptr(out.J_old),

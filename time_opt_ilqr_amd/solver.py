@@ -110,7 +110,9 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
     systems take the point-mass ``obstacles`` table).  A systems.Fleet built with a
     systems.Proximity carries its stage cost itself: its Taylor terms
     (engine.fleet_proximity_cost) feed the select under both methods and the Riccati pass,
-    and the line search evaluates it at every candidate's state, all on the device.
+    and the line search evaluates it at every candidate's state, all on the device.  A
+    systems.Team that carries one (Team.with_proximity) does the same through
+    engine.team_proximity_cost.
     """
     if method == "onepass":
         from . import onepass
@@ -158,8 +160,13 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
         else:
             sid = engine.system_id(system)
         n, m = engine.system_dims(sid)
-    # a fleet with a systems.Proximity: engine.forward_linesearch runs its proximity entry
-    prox = not host and engine.fleet_proximity(sid) is not None
+    # a fleet or a team with a systems.Proximity: engine.forward_linesearch runs its
+    # proximity entry
+    prox = None
+    if not host and engine.fleet_proximity(sid) is not None:
+        prox = engine.fleet_proximity_cost
+    elif not host and engine.team_proximity(sid) is not None:
+        prox = engine.team_proximity_cost
     dev = device or torch.device("cuda", torch.cuda.current_device())
     f64 = torch.float64
     tt = lambda a: torch.as_tensor(np.asarray(a, dtype=float) if not isinstance(  # noqa: E731
@@ -265,8 +272,8 @@ def ilqr_timeopt_batch(system, x0, xg, u_ref, Q, R, Qf, w, N: int, T_min: int, T
         if obs is not None:
             c, cx, cxx = engine.obstacle_cost(s.X[:, :N], obs)
             ex = dict(qxx_extra=cxx, qx_extra=cx, c_extra=c)
-        elif prox:  # a fleet's proximity cost: its Taylor terms feed the select and Riccati
-            c, cx, cxx = engine.fleet_proximity_cost(sid, s.X[:, :N])
+        elif prox:  # a fleet's or a team's proximity cost: its Taylor terms feed the select
+            c, cx, cxx = prox(sid, s.X[:, :N])  # and the Riccati pass
             ex = dict(qxx_extra=cxx, qx_extra=cx, c_extra=c)
         elif host and extra_stage_cost is not None:
             parts = [host_dynamics.stage_cost_terms(extra_stage_cost, Xh[b], Uh[b])

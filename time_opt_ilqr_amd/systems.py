@@ -558,7 +558,20 @@ class Team:
     numbers bit for bit.  ``wrap_idx`` and ``position_idx`` hold the members' angle and
     position indices shifted by their offsets.  Calling it evaluates a NumPy twin of F on
     the host (one state, or stacked rows), so ``host()`` wraps the same team for comparison.
-    A team takes no proximity cost: its members' positions differ in dimension."""
+
+    ``with_proximity(prox)`` returns the same team carrying a :class:`Proximity` as a stage
+    cost evaluated on the device (include/hop_mixed_proximity.h); ``proximity`` is None
+    otherwise.  The members' positions differ in dimension (``pos_dims``), so they live in a
+    common workspace of dimension ``pos_dim`` = max(pos_dims): member a's workspace position
+    is its leading ``pos_dims[a]`` state entries padded with zeros -- a DI moves on the x
+    axis, a point mass in the plane z = 0, a quadrotor in space -- the obstacle table is
+    [K, pos_dim + 2], and a bump's gradient and second-order block are restricted to the
+    coordinates a member has.  engine.cost_true, engine.forward_linesearch and the solver
+    functions then run the proximity entries, and ``stage_cost()`` is the NumPy twin; a team
+    of equal members computes the numbers of that :class:`Fleet` with the same cost bit for
+    bit."""
+
+    proximity = None
 
     def __init__(self, members, dt=None):
         try:
@@ -603,6 +616,64 @@ class Team:
         self.position_idx = [xo + i for s, xo in zip(ids, self.x_offsets)
                              for i in _MEMBERS[s][4]]
         self.name = "team_" + "+".join(_MEMBERS[s][2] for s in ids)
+        self.pos_dims = tuple(len(_MEMBERS[s][4]) for s in ids)
+        self.pos_dim = max(self.pos_dims)
+
+    def with_proximity(self, prox):
+        """A new team, equal otherwise, that carries the :class:`Proximity` ``prox`` (its
+        obstacle table in ``pos_dim`` + 2 columns)."""
+        if not isinstance(prox, Proximity):
+            raise TypeError("Team.with_proximity: prox must be a systems.Proximity")
+        prox.check_pos_dim(self.pos_dim)
+        out = Team(self.member_ids, dt=self.dt)
+        out.proximity = prox
+        return out
+
+    def stage_cost(self):
+        """The proximity cost as a NumPy callable (x, u) -> (c, cx [n], cxx [n, n]): what
+        ``host()`` users pass as ``extra_stage_cost``, and the twin the device kernels are
+        tested against.  Zeros for a team without a proximity cost."""
+        n, D, count = self.n, self.pos_dim, len(self.member_ids)
+        xo, pds = self.x_offsets, self.pos_dims
+        prox = self.proximity
+        rows = np.zeros((0, D + 2)) if prox is None else prox.table(D)
+        r_s, w_s = (1.0, 0.0) if prox is None else prox.sep()
+
+        def cost(x, u=None):
+            x = np.asarray(x, dtype=float).reshape(-1)
+            p = np.zeros((count, D))
+            for a in range(count):
+                p[a, :pds[a]] = x[xo[a]:xo[a] + pds[a]]
+            c, cx, cxx = 0.0, np.zeros(n), np.zeros((n, n))
+
+            def add(a, b, d, r, w):  # one bump between member a and an obstacle or member b
+                nonlocal c
+                ci = w * np.exp(-float(d @ d) / (2.0 * r * r))
+                g, H = -(ci / (r * r)) * d, ci * np.outer(d, d) / r ** 4
+                pa = pds[a]
+                sa = slice(xo[a], xo[a] + pa)
+                c += ci
+                cx[sa] += g[:pa]
+                cxx[sa, sa] += H[:pa, :pa]
+                if b is not None:
+                    pb = pds[b]
+                    sb = slice(xo[b], xo[b] + pb)
+                    cx[sb] -= g[:pb]
+                    cxx[sb, sb] += H[:pb, :pb]
+                    cxx[sa, sb] -= H[:pa, :pb]
+                    cxx[sb, sa] -= H[:pb, :pa]
+
+            for a in range(count):
+                for row in rows:
+                    if row[D + 1] != 0.0:
+                        add(a, None, p[a] - row[:D], row[D], row[D + 1])
+                if w_s != 0.0:
+                    for b in range(a + 1, count):
+                        add(a, b, p[a] - p[b], r_s, w_s)
+            return c, cx, cxx
+
+        cost.proximity = prox
+        return cost
 
     def team_params(self):
         """(member system ids, dt): what the hop_team_* entries take."""
@@ -675,6 +746,46 @@ def make_team(members, N=None, seed=0, coupling=0.5, w_scale=1.0, T_min=None, dt
         Q[j, i] -= kappa
     Qf = _blocks([mk[6] * np.eye(len(mk[1])) if np.ndim(mk[6]) == 0 else mk[6] for mk in mks])
     return (F, x0, np.concatenate([np.asarray(mk[2], dtype=float) for mk in mks]),
+            np.concatenate([np.atleast_1d(np.asarray(mk[3], dtype=float)) for mk in mks]), Q,
+            _blocks([mk[5] for mk in mks]), Qf, float(w_scale) * max(float(mk[7]) for mk in mks),
+            N, int(max(int(mk[9]) for mk in mks) if T_min is None else T_min),
+            int(min(min(int(mk[10]) for mk in mks), N - 5)), list(F.wrap_idx), None)
+
+
+def make_team_crossing(members, N=None, seed=0, w_scale=1.0, q_pos=0.5, bump_weight=1.5,
+                       T_min=None, dt=None):
+    """A crossing problem of mixed members with a proximity cost
+    (tests/golden/make_golden_team_proximity.py's): :func:`make_fleet_crossing`'s recipe on
+    the members of a :class:`Team`.  Every member's maker is called with the team's dt and N,
+    and N, T_min and T_max follow :func:`make_team`'s rules; there is no Laplacian coupling.
+    The starts' position entries lie on the circle of radius 2, member a at angle
+    2 pi a / count + 0.15 N(0, 1) from ``seed`` taking the circle's first ``pos_dims[a]``
+    coordinates; the goals are the starts turned by 2.2 rad.  Q gets ``q_pos`` added on the
+    position entries, one obstacle sits at (0.3, 0.2, 0)[:pos_dim] with radius 0.5, the
+    separation radius is 0.4, and both bumps weigh ``bump_weight``.  Returns the usual
+    13-tuple with F a :class:`Team` that carries the :class:`Proximity`."""
+    F0 = Team(members, dt=dt)
+    if N is None:
+        N = min(int(_MEMBER_MAKERS[s]()[8]) for s in F0.member_ids)
+    N = int(N)
+    mks = [_MEMBER_MAKERS[s](dt=F0.dt, N=N) for s in F0.member_ids]
+    D, count = F0.pos_dim, len(F0.member_ids)
+    prox = Proximity(
+        obstacles=[list(CROSSING_OBSTACLE[:D]) + [CROSSING_OBS_RADIUS, float(bump_weight)]],
+        separation=(CROSSING_SEP_RADIUS, float(bump_weight)))
+    F = F0.with_proximity(prox)
+    rng = np.random.default_rng(seed)
+    ang = 2.0 * np.pi * np.arange(count) / count + CROSSING_JITTER * rng.standard_normal(count)
+    x0 = np.concatenate([np.asarray(mk[1], dtype=float) for mk in mks])
+    xg = np.concatenate([np.asarray(mk[2], dtype=float) for mk in mks])
+    for a, (xo, pd) in enumerate(zip(F.x_offsets, F.pos_dims)):
+        for ang_a, x in ((ang[a], x0), (ang[a] + CROSSING_TURN, xg)):
+            circle = CROSSING_RADIUS * np.array([np.cos(ang_a), np.sin(ang_a), 0.0])
+            x[xo:xo + pd] = circle[:pd]
+    Q = _blocks([mk[4] for mk in mks])
+    Q[F.position_idx, F.position_idx] += float(q_pos)
+    Qf = _blocks([mk[6] * np.eye(len(mk[1])) if np.ndim(mk[6]) == 0 else mk[6] for mk in mks])
+    return (F, x0, xg,
             np.concatenate([np.atleast_1d(np.asarray(mk[3], dtype=float)) for mk in mks]), Q,
             _blocks([mk[5] for mk in mks]), Qf, float(w_scale) * max(float(mk[7]) for mk in mks),
             N, int(max(int(mk[9]) for mk in mks) if T_min is None else T_min),

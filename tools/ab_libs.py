@@ -1,6 +1,6 @@
 """Same-process interleaved A/B of two (or more) builds of libhop_amd.so on the bench
 workloads (config 3 tile64 fp32, config 2 fp64, config 4 shard, Riccati mode 0/1, the
-forward pass, and the row-layout device systems' four entries: row_system_workloads):
+forward pass, and the row-layout device systems' entries: row_system_workloads):
 
     python tools/ab_libs.py time_opt_ilqr_amd/libhop_amd.so <other.so> [--rounds 7]
 
@@ -31,7 +31,8 @@ def row_system_workloads(work, dev, kw):
     """rollout, central linearisation, cost_true and forward_linesearch of the row-layout
     device systems (csrc/row_system.hpp) at B = 4096: the chain of tools/bench_chain.py
     (p = 12, m = 3, N = 60) and the fleets of tools/bench_fleet.py (quadrotor x 2 at
-    N = 80, double integrator x 15 at N = 60); every output of every entry."""
+    N = 80, double integrator x 15 at N = 60), and all six entries of the team of
+    tools/bench_team.py (quadrotor + 3 point masses, N = 80); every output of every entry."""
     import torch
     from time_opt_ilqr_amd import engine, systems
     from time_opt_ilqr_amd.utils import as_terminal_weight
@@ -45,6 +46,10 @@ def row_system_workloads(work, dev, kw):
         F, x0, xg, ur, Q, R, Qf, w, N, _, T_max, wrap, _ = systems.make_fleet(
             base, count, N=N, seed=7000, w_scale=100.0)
         problems[tag] = (F, x0, xg, ur, Q, R, Qf, w, N, T_max, wrap, 0.05)
+    # a team (quadrotor + 3 point masses, tools/bench_team.py's): its six entries
+    F, x0, xg, ur, Q, R, Qf, w, N, _, T_max, wrap, _ = systems.make_team(
+        (2, 3, 3, 3), N=80, seed=7000, w_scale=1600.0, T_min=15)
+    problems["team_quad_pm3"] = (F, x0, xg, ur, Q, R, Qf, w, N, T_max, wrap, 0.002)
     for tag, (F, x0, xg, ur, Q, R, Qf, w, N, T_max, wrap, du) in problems.items():
         n, m = engine.system_dims(F)
         x0b = tt(x0) + 0.05 * torch.randn((Bn, n), **kw)
@@ -71,6 +76,14 @@ def row_system_workloads(work, dev, kw):
         work[f"{tag}_cost_true"] = (lambda F=F, X=X, U=U, T=T, cost=cost:
                                     engine.cost_true(F, X, U, T, cost))
         work[f"{tag}_linesearch"] = linesearch
+        if engine.is_team(F):
+            Xs, Us = X[:, :N].reshape(-1, n).contiguous(), U.reshape(-1, m).contiguous()
+            work[f"{tag}_dynamics"] = lambda F=F, Xs=Xs, Us=Us: engine.dynamics(F, Xs, Us, F.dt)
+
+            def linearize_forward(F=F, X=X, U=U):
+                r = engine.linearize(F, X, U, F.dt, central=False)
+                return r.A, r.B, r.a_res
+            work[f"{tag}_linearize_forward"] = linearize_forward
 
 
 def main():
