@@ -56,7 +56,11 @@ def _wide_sweep(dev, A, Bm, Q, Ri, z0, QT, t_min=0, t_max=0):
 # 1 -------------------------------------------------------------------------
 @pytest.mark.parametrize("s,m,N,Bn", [(17, 4, 12, 5), (24, 6, 12, 5), (31, 3, 12, 5),
                                       (32, 8, 12, 5), (32, 16, 6, 3), (20, 1, 40, 3),
-                                      (32, 8, 1, 2)])
+                                      (32, 8, 1, 2),
+                                      # HR = 14 (s = 25 .. 28): both ends, and the neighbours
+                                      # on either side (s = 29: HR = 16, s = 21: HR = 12)
+                                      (25, 4, 12, 5), (28, 8, 12, 5), (29, 4, 12, 3),
+                                      (21, 3, 12, 3)])
 def test_wide_block_form_vs_oracle(dev, s, m, N, Bn):
     from time_opt_ilqr_amd import engine
     A, Bm, Q, R, Ri, z0, QT = orc.synth_lft_batch(7000 + s, Bn, s, m, N)
